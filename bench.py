@@ -9,6 +9,12 @@ A step = one full training iteration of the hot path on one batch: MsVFMEncoderD
 sample -> LR 512^2 pass + HR 512^2 crop through the 24-block backbone, both heads, two fused upsample-CE losses),
 backward (LoRA + head gradients), DP gradient all-reduce, fused AdamW, zero_grad.  One "image" = one dataloader
 sample.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the headline line.  --full adds everything else the line
+has carried: the sampled-HIP-event roofline of the timed steps, the eval ms/img leg, configs[3], the in-tolerance
+precision modes, the fp16 `--amp` step, the CPU baseline and (N > 1) the per-rank diagnostics; --no-roofline / --no-eval /
+--no-parity-mode / --no-cpu-baseline drop single parts of it.  --dump-outputs DIR writes what the last timed step
+returned (its log_vars) and a fixed sample of the trainable parameters after it as .npy.
 """
 import argparse
 import json
@@ -437,6 +443,26 @@ def cpu_baseline(seconds_cap=40.0, model_kw=None):
     return out
 
 
+DUMP_SAMPLE = 1 << 20   # trainable values --dump-outputs keeps: the flat buffer holds ~16.6 M (66 MB in fp32)
+
+
+def dump_sample_index(n, device):
+    """Fixed, seeded positions (sorted) in the flat trainable buffer: the same for every run of the same configuration."""
+    g = torch.Generator().manual_seed(0)
+    return torch.randperm(n, generator=g)[:min(n, DUMP_SAMPLE)].sort().values.to(device)
+
+
+def dump_outputs(out_dir, log_vars, params):
+    """--dump-outputs: the last timed step's log_vars (float64) and the sampled trainable parameters after it (float32), one
+    DIR/<name>.npy each."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v.detach().double().cpu() if torch.is_tensor(v) else v, dtype=np.float64) for k, v in log_vars.items()}
+    arrays["trainable_params_sample"] = params.cpu().numpy()
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k.replace(os.sep, "_") + ".npy"), v)
+    return sorted(arrays)
+
+
 def _pin_this_rank():
     """Started by torchrun (the driver's form) rather than by tools/dist_launch.py: this rank pins itself - before torch and the HIP
     runtime start their threads - to the cores the launcher would have given it (tools/dist_launch.py:rank_cpus)."""
@@ -521,10 +547,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=2, help="samples per GPU (reference: 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-eval", action="store_true", help="skip the eval ms/img @1024x1024 leg (N=1 only)")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the f32 parity-mode speed leg (N=1 only)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, eval, configs[3], parity-mode, fp16 --amp and CPU-baseline legs "
+                                                          "and (N > 1) the per-rank diagnostics; off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's log_vars and a fixed sample of the trainable parameters after it to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the sampled-event roofline of the timed steps")
+    ap.add_argument("--no-eval", action="store_true", help="with --full: skip the eval ms/img @1024x1024 and configs[3] legs (N=1 only)")
+    ap.add_argument("--no-parity-mode", action="store_true", help="with --full: skip the parity-mode and fp16 --amp speed legs (N=1 only)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "bf16x3", "fp16"])
     ap.add_argument("--workload", default="ms1024", choices=["ms1024", "single512"],
                     help="ms1024: BASELINE configs[1] (1024^2 sample -> LR + HR 512^2 passes, both heads; the headline metric); "
@@ -586,9 +616,11 @@ def main():
     from vfmseg_amd import functional as Fh
     Fh.manual_seed(1234 + rank)
     data = make_batch(a.batch, rank, 0, device, size=1024 if a.workload == "ms1024" else 512)
+    roofline = a.full and not a.no_roofline
     timer = KernelTimer()
-    if not a.no_roofline:
+    if roofline:
         timer.install()
+    dump_idx = dump_sample_index(ow.optimizer.flat.numel(), device) if a.dump_outputs and rank == 0 else None
 
     def barrier():
         if world > 1:
@@ -600,26 +632,29 @@ def main():
         model.train_step(data, ow)
     barrier()
     print(f"[bench] rank {rank}: timing {a.steps} steps", file=sys.stderr, flush=True)
-    timer.on = not a.no_roofline
+    timer.on = roofline
     gs = getattr(ow, "grad_sync", None)
-    if gs is not None and world > 1:
+    if gs is not None and world > 1 and a.full:
         gs.measure = True          # event pair around the join of the all-reduce stream: what backward did NOT hide
     host_s = 0.0
     t0 = time.perf_counter()
     for _ in range(a.steps):
         h0 = time.perf_counter()
-        model.train_step(data, ow)
+        log_vars = model.train_step(data, ow)
         host_s += time.perf_counter() - h0
     torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0      # this rank's own clock, before it waits for the others
     barrier()
     dt = time.perf_counter() - t0
     timer.on = False
+    if dump_idx is not None:
+        dump_outputs(a.dump_outputs, log_vars, ow.optimizer.flat[dump_idx])
     ranks = None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if world > 1 and a.full:
         # per-rank diagnostics for rank 0's line: a slow or host-bound rank, an exposed all-reduce and a bad core assignment show here
         exposed = gs.exposed_ms() if gs is not None and hasattr(gs, "exposed_ms") else float("nan")
         try:
@@ -664,10 +699,10 @@ def main():
         out["config"]["workload"] = "single-pass variant of configs[1]: EncoderDecoder(LoRABackbone(DINOv2-L), LinearHead), 512^2 inputs, bs=%d/GPU" % a.batch
     if rank == 0:
         GEMMS = ("gemm", "gemm_tn")
-        allg = timer.summary(kinds=GEMMS)
+        allg = timer.summary(kinds=GEMMS) if roofline else None
         # the dominant kernel family: k_gemm_w4 (LDS-DMA chunk ring; 128x128 and 256x256 tile forms) = the backbone's QKV / proj / fc1 / fc2
         # forward and input-gradient launches (>= 8.6 GFLOP each; 193 launches and ~47 % of the step's GPU time in profiles/*_kernel_stats.csv)
-        g = timer.summary(kinds=("gemm",), region="backbone", min_flops=8e9) or allg
+        g = (timer.summary(kinds=("gemm",), region="backbone", min_flops=8e9) or allg) if roofline else None
         if g is not None:
             traffic, traffic_src = None, None
             for tj_name in ("r04_pmc_gemm_traffic.json", "r03_pmc_gemm_traffic.json", "r02_pmc_gemm_traffic.json", "r01_pmc_gemm_traffic.json"):
@@ -710,19 +745,19 @@ def main():
         # end-to-end model-FLOP utilisation (722.4 GFLOP fwd per image-pass, train ~2.2x, 2 passes/sample)
         out["model_tflops"] = round(value / world * (2 if a.workload == "ms1024" else 1) * 722.4e9 * 2.2 / 1e12, 2)
         out["model_frac"] = round(out["model_tflops"] / PEAK_BF16_TFLOPS, 4)
-        if world == 1 and not a.no_eval and a.workload == "ms1024":
+        if world == 1 and a.full and not a.no_eval and a.workload == "ms1024":
             del model, ow, data
             torch.cuda.empty_cache()
             try:
-                out["eval"] = eval_leg(device, timer if not a.no_roofline else None)
+                out["eval"] = eval_leg(device, timer if roofline else None)
             except Exception as e:
                 out["eval"] = {"error": repr(e)}
-        if world == 1 and not a.no_eval and a.workload == "ms1024" and a.dtype == "bf16" and a.depth is None:
+        if world == 1 and a.full and not a.no_eval and a.workload == "ms1024" and a.dtype == "bf16" and a.depth is None:
             try:
-                out["other_backbones"] = other_backbones_leg(device, a.batch, timer if not a.no_roofline else None)
+                out["other_backbones"] = other_backbones_leg(device, a.batch, timer if roofline else None)
             except Exception as e:
                 out["other_backbones"] = {"error": repr(e)}
-        if world == 1 and not a.no_parity_mode and a.workload == "ms1024" and a.dtype == "bf16" and a.depth is None:
+        if world == 1 and a.full and not a.no_parity_mode and a.workload == "ms1024" and a.dtype == "bf16" and a.depth is None:
             try:
                 out["parity_mode"] = parity_leg(device, a.batch)
             except Exception as e:
@@ -732,7 +767,7 @@ def main():
                                        what="tools/train.py --amp: fp16 storage + v_mfma_f32_32x32x16_f16 (libvfmseg_hip_f16.so), AmpOptimWrapper")
             except Exception as e:
                 out["amp_fp16"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline and a.workload == "ms1024":
+        if world == 1 and a.full and not a.no_cpu_baseline and a.workload == "ms1024":
             try:
                 out["cpu_baseline"] = cpu_baseline_guarded()
             except Exception as e:  # the baseline must never take the GPU number down with it

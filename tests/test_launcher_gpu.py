@@ -17,7 +17,7 @@ def test_bench_two_ranks_share_the_gpu():
     env = dict(os.environ, VFMSEG_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--depth", "4", "--steps", "3", "--warmup", "2", "--no-eval",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--depth", "4", "--steps", "3", "--warmup", "2", "--full", "--no-eval",
                         "--no-cpu-baseline", "--no-parity-mode", "--launch-timeout", "500"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
