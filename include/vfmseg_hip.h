@@ -302,10 +302,12 @@ int vfm_assemble_tokens(const float* patch_tok, const float* cls, const float* p
  * (y0,x0,hc,wc) is produced.  out layout: out_mode 0 = NHWC [B,hc,wc,ldc_out] (C valid, rest zero),
  * 1 = NCHW [B,C,hc,wc], 2 = NHWC with 2-level 2x2 blocked pixel order (b, y/4, x/4, (y/2)%2, (x/2)%2, y%2, x%2, C)
  * so that stride-2 2x2 convolutions become GEMMs on views (VFMHead.py:38-45).  (Ms_VFM_encoder_decoder.py:129-133,
- * 160-167; VFMHead.py:63-67; linear_head.py:76-80) */
+ * 160-167; VFMHead.py:63-67; linear_head.py:76-80).  scale_y / scale_x: source pixels per output pixel; 0 = Hi/Hv, Wi/Wv
+ * (F.interpolate(size=...)).  F.interpolate(scale_factor=s) samples with 1/s instead, which differs from in/out whenever the
+ * output size floor(in*s) is not exact (odd sizes at s=0.5): pass 1/s then. */
 int vfm_resize_bilinear(const void* in, int in_dt, int in_nchw, int B, int Hi, int Wi, int C, long in_ld_c, void* out,
                         int out_dt, int out_mode, long out_ld_c, int Hv, int Wv, int y0, int x0, int hc, int wc,
-                        void* stream);
+                        float scale_y, float scale_x, void* stream);
 /* bicubic (A=-0.75, align_corners=False, explicit source scales as F.interpolate(scale_factor=...) passes them) on a
  * token-major fp32 map [Hi,Wi,C] -> [Ho,Wo,C]: DINOv2 pos-embed re-interpolation (dino_v2.py:184-215) */
 int vfm_resize_bicubic(const float* in, int Hi, int Wi, int C, float* out, int Ho, int Wo, float scale_y, float scale_x,

@@ -40,10 +40,12 @@ def mask_digest(m):
     return hashlib.sha256(np.ascontiguousarray(m.astype(np.uint8)).tobytes()).hexdigest()
 
 
-def build_reference_model(depth=24):
+def build_reference_model(depth=24, out_indices=None):
     """The reference's MsVFMEncoderDecoder with synthetic parameters."""
     M = ref_shim.load_all()
     cfg = presets.dinov2_ms_masked(depth=depth)
+    if out_indices is not None:
+        cfg["backbone"]["backbone"]["out_indices"] = list(out_indices)
     # LoRABackbone loads a checkpoint unconditionally (lora_backbone.py:27-35): give it one, in the
     # *un-renamed* key scheme the converters emit, so the reference's own rename path runs.
     bb = M.build(cfg["backbone"]["backbone"])
@@ -302,6 +304,111 @@ def gen_slide_modes(model):
     np.savez_compressed(os.path.join(GOLD, "slide_modes.npz"), **out)
 
 
+# The reference's DG evaluation sizes (test pipelines' keep-ratio resizes): Cityscapes 1024 x 2048 (3 x 6 windows), ACDC 1080 x 1920
+# (3 x 6, ragged last row / column), BDD100k 720 x 1280 (2 x 4, ragged last row), a Mapillary photo 1024 x 1365 (3 x 4, odd width).
+EVAL_SIZES = ((1024, 2048), (1080, 1920), (720, 1280), (1024, 1365))
+EVAL_SIZES_DEPTH = 4      # window / resize / gate code does not depend on depth; full-depth parity is pinned at 1024^2
+
+
+def eval_sizes_seed(h, w):
+    return 500 + (h * 7 + w) % 97
+
+
+def eval_sizes_probes(h, w, boxes):
+    """(name, (y0, y1, x0, x1)) logit windows stored per size: a corner, the centre, a seam between the first two window columns
+    (where an overlap band starts), and the bottom-right edge (the ragged last window row / column)."""
+    seam_x = boxes[1][2] if len(boxes) > 1 and boxes[1][2] > 0 else w // 2
+    return (("corner", (0, 8, 0, 8)), ("centre", (h // 2 - 2, h // 2 + 2, w // 2 - 4, w // 2 + 4)),
+            ("seam", (h // 3, h // 3 + 4, seam_x - 4, seam_x + 4)), ("edge", (h - 4, h, w - 8, w)))
+
+
+def eval_sizes_gate(seg, boxes, thrs=(0.2, 0.25, 0.3, 0.35, 0.4, 0.45, 0.5)):
+    """(thr, conf) for which some windows of `boxes` are refined and some are not, with conf in the middle of the widest gap between
+    the windows' gate fractions (so that rounding of the coarse logits cannot move a window across it)."""
+    best = None
+    for thr in thrs:
+        conf_map = (seg.softmax(dim=1).max(dim=1)[0] > thr).double()
+        fr = sorted(conf_map[:, y1:y2, x1:x2].mean().item() for (y1, y2, x1, x2) in boxes)
+        for k in range(len(fr) - 1):
+            gap = fr[k + 1] - fr[k]
+            if best is None or gap > best[0]:
+                best = (gap, thr, round((fr[k] + fr[k + 1]) / 2, 4))
+    assert best is not None and best[0] > 0.008, ("no threshold separates the windows", best)
+    return best[1], best[2]
+
+
+def gen_eval_sizes(_model=None):
+    """MsVFMEncoderDecoder.inference of the reference at its DG evaluation sizes (EVAL_SIZES; depth 4, out_indices 0-3): ms_slide_inference
+    everywhere (gate thresholds per size chosen so that some windows are refined and some are not; the refined boxes recorded), and
+    lr_slide_inference where the half-size image is at least one crop tall.  Pins the oracle (tests/test_oracle_golden.py) and the HIP
+    path (tests/test_eval_sizes_gpu.py) where the window grid has more than 16 windows, ragged rows / columns, non-integer resize factors,
+    context windows off the coarse grid, and an odd width."""
+    model = build_reference_model(depth=EVAL_SIZES_DEPTH, out_indices=range(EVAL_SIZES_DEPTH))
+    out = {"sizes": np.array(EVAL_SIZES), "test_cfg_stride_crop": np.array(list(model.test_cfg["stride"]) + list(model.test_cfg["crop_size"]))}
+    orig = model.enc_dec
+    refined = []
+
+    def spy(inputs, context=None):
+        if context is not None:
+            refined.append(tuple(int(v) for v in model.hr_crop_box))
+        return orig(inputs, context)
+
+    def run(img, mode):
+        reset(model)
+        model.eval()
+        model.test_cfg["mode"] = mode
+        h, w = img.shape[2:]
+        metas = [dict(ori_shape=(h, w), img_shape=(h, w), pad_shape=(h, w), padding_size=[0, 0, 0, 0])]
+        refined.clear()
+        with torch.no_grad():
+            return model.inference(img, metas)
+
+    model.enc_dec = spy
+    for (h, w) in EVAL_SIZES:
+        img = synth_image(1, (h, w), seed=eval_sizes_seed(h, w))
+        boxes = [tuple(b) for b in ref_shim_grid(h, w, model)]
+        # the coarse map alone: a gate that refines nothing leaves every window's coarse logits (merge of equal values)
+        model.test_cfg["threadshod"], model.test_cfg["conf"] = 0.5, -1.0
+        seg = run(img, "ms_slide_inference")
+        assert not refined
+        thr, conf = eval_sizes_gate(seg, boxes)
+        model.test_cfg["threadshod"], model.test_cfg["conf"] = thr, conf
+        modes = ["ms_slide_inference"] + (["lr_slide_inference"] if h // 2 >= model.test_cfg["crop_size"][0] else [])
+        for mode in modes:
+            logits = run(img, mode)
+            key = f"{h}x{w}/{mode}::"
+            if mode == "ms_slide_inference":
+                assert 0 < len(refined) < len(boxes), (h, w, len(refined), len(boxes))
+                out[key + "test_cfg"] = np.array([thr, conf])
+                out[key + "refined_boxes"] = np.array(refined).reshape(-1, 4)
+            else:
+                assert not refined
+            oh, ow = logits.shape[2:]
+            assert (oh, ow) == ((h, w) if mode == "ms_slide_inference" else (h // 2 * 2, w // 2 * 2)), logits.shape
+            pred = logits.argmax(dim=1)[0].numpy().astype(np.uint8)
+            out[key + "logits_stats"] = stats(logits)
+            for name, (y0, y1, x0, x1) in eval_sizes_probes(oh, ow, boxes):
+                out[key + "logits_" + name] = logits[0, :, y0:y1, x0:x1].numpy().copy()
+            out[key + "pred_sub8"] = pred[::8, ::8].copy()
+            out[key + "pred_sha256"] = np.array(mask_digest(pred))
+            out[key + "pred_hist"] = np.bincount(pred.reshape(-1), minlength=19)
+            print(f"eval_sizes {h}x{w} {mode}: windows {len(boxes)}, refined {len(refined)} (thr {thr}, conf {conf}),",
+                  out[key + "logits_stats"], out[key + "pred_sha256"][()][:12])
+    model.enc_dec = orig
+    np.savez_compressed(os.path.join(GOLD, "eval_sizes.npz"), **out)
+
+
+def ref_shim_grid(h, w, model):
+    """The window grid of the reference's slide loops (Ms_VFM_encoder_decoder.py:428-443) for the model's test_cfg."""
+    (hs, ws), (hc, wc) = model.test_cfg["stride"], model.test_cfg["crop_size"]
+    boxes = []
+    for hi in range(max(h - hc + hs - 1, 0) // hs + 1):
+        for wi in range(max(w - wc + ws - 1, 0) // ws + 1):
+            y2, x2 = min(hi * hs + hc, h), min(wi * ws + wc, w)
+            boxes.append((max(y2 - hc, 0), y2, max(x2 - wc, 0), x2))
+    return boxes
+
+
 def gen_eva02(_model=None):
     """EVA02-L + LoRA (q/k/v/attn.proj targets; only attn.proj is live): taps and LoRA gradients."""
     M = ref_shim.load_eva02()
@@ -546,6 +653,8 @@ def main():
         gen_rcs()
     if a.only in (None, "sam_slide"):
         gen_sam_slide()
+    if a.only in (None, "eval_sizes"):
+        gen_eval_sizes()
 
 
 if __name__ == "__main__":

@@ -317,3 +317,50 @@ def test_amp_emulation_of_forward_train_is_an_fp16_sized_perturbation():
     for k in ("decode_lr.loss_ce", "decode_hr.loss_ce"):
         e = abs(float(l16[k]) - float(l32[k])) / abs(float(l32[k]))
         assert 0 < e < 2e-3, (k, e)
+
+
+def _eval_sizes_checks(G, key, lg, tol, mism_tol):
+    """The eval_sizes.npz probes of one (size, mode) against logits lg [1, 19, h, w] (shared with tests/test_eval_sizes_gpu.py)."""
+    from oracle.gen_golden import eval_sizes_probes
+    h, w = lg.shape[2:]
+    boxes = R.grid_boxes(h, w)
+    for name, (y0, y1, x0, x1) in eval_sizes_probes(h, w, boxes):
+        assert rel_err(lg[0, :, y0:y1, x0:x1], G[key + "logits_" + name]) < tol, (key, name)
+    pred = lg.argmax(dim=1)[0].cpu().numpy().astype(np.uint8)
+    assert pred[::8, ::8].shape == G[key + "pred_sub8"].shape
+    assert (pred[::8, ::8] != G[key + "pred_sub8"]).mean() < mism_tol, key
+    return pred
+
+
+@pytest.mark.slow
+def test_eval_sizes_inference(golden_dir):
+    """The oracle's ms_inference / lr_slide_inference at the reference's DG evaluation sizes (1024x2048, 1080x1920, 720x1280, 1024x1365;
+    tests/golden/eval_sizes.npz, written by oracle.gen_golden --only eval_sizes from the reference's own MsVFMEncoderDecoder.inference,
+    depth 4): which windows the gate refines, and the logits at a corner, the centre, a window seam and the ragged edge."""
+    from tests.helpers import full_state_dict
+    G = _g(golden_dir, "eval_sizes.npz")
+    from oracle.gen_golden import eval_sizes_seed
+    sd = full_state_dict(depth=4)
+    kw = dict(depth=4, out_indices=(0, 1, 2, 3))
+    stride, crop = tuple(int(v) for v in G["test_cfg_stride_crop"][:2]), tuple(int(v) for v in G["test_cfg_stride_crop"][2:])
+    seen = 0
+    for h, w in G["sizes"].tolist():
+        img = synth_image(1, (h, w), seed=eval_sizes_seed(h, w))
+        for mode in ("ms_slide_inference", "lr_slide_inference"):
+            key = f"{h}x{w}/{mode}::"
+            if key + "logits_stats" not in G.files:
+                continue
+            seen += 1
+            with torch.no_grad():
+                if mode == "ms_slide_inference":
+                    thr, conf = G[key + "test_cfg"]
+                    trace = []
+                    lg = R.ms_inference(sd, img, thr=float(thr), conf=float(conf), crop=crop, stride=stride, trace=trace, **kw)
+                    assert np.array_equal(np.array(trace).reshape(-1, 4), G[key + "refined_boxes"]), key
+                else:
+                    lg = R.lr_slide_inference(sd, img, crop, stride, **kw)
+            assert tuple(lg.shape[2:]) == ((h, w) if mode == "ms_slide_inference" else (h // 2 * 2, w // 2 * 2))
+            _eval_sizes_checks(G, key, lg, 1e-4, 2e-4)
+            np.testing.assert_allclose(stats(lg), G[key + "logits_stats"], rtol=1e-4, atol=1e-6)
+            assert np.abs(np.bincount(lg.argmax(dim=1).reshape(-1).numpy(), minlength=19) - G[key + "pred_hist"]).sum() < 200
+    assert seen == 7

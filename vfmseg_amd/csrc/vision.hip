@@ -133,14 +133,16 @@ __global__ void k_resize_bilinear(const void* __restrict__ in, int in_dt, int in
 }
 extern "C" int vfm_resize_bilinear(const void* in, int in_dt, int in_nchw, int B, int Hi, int Wi, int C, long in_ld_c,
                                    void* out, int out_dt, int out_mode, long out_ld_c, int Hv, int Wv, int y0, int x0, int hc,
-                                   int wc, void* stream) {
+                                   int wc, float scale_y, float scale_x, void* stream) {
   VFM_CHECK(Hv > 0 && Wv > 0 && y0 >= 0 && x0 >= 0 && y0 + hc <= Hv && x0 + wc <= Wv, VFM_E_SHAPE, "vfm_resize_bilinear: window");
+  VFM_CHECK(scale_y >= 0.f && scale_x >= 0.f, VFM_E_INVAL, "vfm_resize_bilinear: negative source scale");
   VFM_CHECK(out_mode != 2 || (hc % 4 == 0 && wc % 4 == 0 && out_ld_c >= 4L * C), VFM_E_SHAPE, "vfm_resize_bilinear: blocked mode needs hc,wc %% 4");
   const long total = (long)B * hc * wc * C;
   if (total == 0) return VFM_OK;
   const int grid = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
   hipLaunchKernelGGL(k_resize_bilinear, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, in_dt, in_nchw, B, Hi, Wi, C, in_ld_c,
-                     out, out_dt, out_mode, out_ld_c, (float)Hi / (float)Hv, (float)Wi / (float)Wv, y0, x0, hc, wc);
+                     out, out_dt, out_mode, out_ld_c, scale_y > 0.f ? scale_y : (float)Hi / (float)Hv,
+                     scale_x > 0.f ? scale_x : (float)Wi / (float)Wv, y0, x0, hc, wc);
   VFM_LAUNCH_CHECK();
   return VFM_OK;
 }

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvfmseg_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvfmseg_hip_f16.so")
 
 F32, BF16, U8, I64, SPLIT3 = 0, 1, 2, 3, 4
-ABI_VERSION = 3   # include/vfmseg_hip.h as of round 4 (vfm_gemm_desc.c_plane): an older in-tree .so would misread the descriptors
+ABI_VERSION = 4   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales: an older in-tree .so would misread the calls
 EP_NONE, EP_GELU, EP_RELU, EP_MUL_GELU_GRAD, EP_MUL, EP_QGELU, EP_MUL_QGELU_GRAD, EP_GELU_DGELU = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_QGELU = 0, 1, 2, 3
 
@@ -151,7 +151,7 @@ SIGNATURES = {
     "vfm_sam_attn_flash_bwd": [vp, cl, vp, vp, vp, vp, vp, cl, vp, vp, vp, vp, cl, ci, ci, ci, ci, ci, cf, vp],
     "vfm_patchify": [vp, cl, cl, cl, ci, ci, ci, ci, ci, vp, ci, cl, ci, vp],
     "vfm_assemble_tokens": [vp, vp, vp, vp, ci, ci, ci, vp],
-    "vfm_resize_bilinear": [vp, ci, ci, ci, ci, ci, ci, cl, vp, ci, ci, cl, ci, ci, ci, ci, ci, ci, vp],
+    "vfm_resize_bilinear": [vp, ci, ci, ci, ci, ci, ci, cl, vp, ci, ci, cl, ci, ci, ci, ci, ci, ci, cf, cf, vp],
     "vfm_resize_bicubic": [vp, ci, ci, ci, vp, ci, ci, cf, cf, vp],
     "vfm_label_resize": [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, vp],
     "vfm_unblock": [vp, vp, ci, ci, ci, ci, ci, ci, vp],

@@ -936,15 +936,22 @@ def assemble_tokens(patch_tok, cls, pos, x, B, np_, C_):
     return x
 
 
-def resize_bilinear(inp, in_nchw, B, Hi, Wi, Cc, out, out_mode, virt, window=None, in_ld=None, out_ld=None):
-    """virt=(Hv,Wv) virtual output size; window=(y0,x0,hc,wc) (default: whole). out_mode 0 NHWC, 1 NCHW, 2 blocked."""
+def resize_bilinear(inp, in_nchw, B, Hi, Wi, Cc, out, out_mode, virt, window=None, in_ld=None, out_ld=None, scale_factor=None):
+    """virt=(Hv,Wv) virtual output size; window=(y0,x0,hc,wc) (default: whole). out_mode 0 NHWC, 1 NCHW, 2 blocked.
+    scale_factor=None samples like F.interpolate(size=virt); a number s (or a pair) like F.interpolate(scale_factor=s), whose source
+    scale is 1/s rather than in/out (they differ when in*s is not a whole number); virt must then be floor(in*s)."""
     lib = L.load()
     Hv, Wv = virt
     y0, x0, hc, wc = window if window is not None else (0, 0, Hv, Wv)
     in_ld = Cc if in_ld is None else in_ld
     out_ld = Cc if out_ld is None else out_ld
+    sy = sx = 0.0
+    if scale_factor is not None:
+        fy, fx = scale_factor if isinstance(scale_factor, (tuple, list)) else (scale_factor, scale_factor)
+        assert (Hv, Wv) == (int(Hi * fy), int(Wi * fx)) and fy > 0 and fx > 0, (virt, Hi, Wi, scale_factor)
+        sy, sx = 1.0 / fy, 1.0 / fx
     L.check(lib.vfm_resize_bilinear(L.ptr(inp), L.dt_of(inp), int(in_nchw), B, Hi, Wi, Cc, in_ld, L.ptr(out), L.dt_of(out),
-                                    out_mode, out_ld, Hv, Wv, y0, x0, hc, wc, L.stream()), "vfm_resize_bilinear")
+                                    out_mode, out_ld, Hv, Wv, y0, x0, hc, wc, sy, sx, L.stream()), "vfm_resize_bilinear")
     return out
 
 

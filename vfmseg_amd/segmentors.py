@@ -224,6 +224,17 @@ class EncoderDecoder(nn.Module):
         return out
 
     @staticmethod
+    def _gate_counts(seg, boxes, thr, cnt):
+        """cnt[j] += the number of pixels of window boxes[j] = (y1, y2, x1, x2) of the NCHW map seg whose max softmax exceeds thr:
+        all windows in one pass (up to 16), else one pass per window."""
+        if len(boxes) <= 16:
+            ops.conf_gate_windows(seg, [(y1, x1, y2 - y1, x2 - x1) for (y1, y2, x1, x2) in boxes], thr, cnt)
+        else:
+            for j, (y1, y2, x1, x2) in enumerate(boxes):
+                ops.conf_gate_count(seg, (y1, x1, y2 - y1, x2 - x1), thr, cnt[j:j + 1])
+        return cnt
+
+    @staticmethod
     def _merge_windows(wins, B, C, H, W, dev):
         """mmseg's slide merge (preds[window] += resize(window logits); count += 1; preds / count) over `wins` = [(logits, nchw, (y0, x0, hc,
         wc))] in accumulation order: one gather pass (vfm_slide_gather), or the per-window accumulate + finalize when the table does not fit."""
@@ -400,8 +411,8 @@ class MsVFMEncoderDecoder(EncoderDecoder):
         assert s1 == 1 and self.crop_size is not None
         lh, lw = int(H * s0), int(W * s0)
         lr_img = torch.empty(B, 3, lh, lw, dtype=torch.float32, device=img.device)
-        ops.resize_bilinear(img, True, B, H, W, 3, lr_img, 1, (lh, lw))
-        box = self.fixed_crop_box or get_crop_bbox(H, W, self.crop_size, self.crop_coord_divisible)
+        ops.resize_bilinear(img, True, B, H, W, 3, lr_img, 1, (lh, lw), scale_factor=s0)
+        box =self.fixed_crop_box or get_crop_bbox(H, W, self.crop_size, self.crop_coord_divisible)
         self.hr_crop_box = box
         y1, y2, x1, x2 = box
         assert (lh, lw) == (y2 - y1, x2 - x1), "LR pass and HR crop must share the token grid to be batched"
@@ -453,18 +464,18 @@ class MsVFMEncoderDecoder(EncoderDecoder):
             return self.lr_slide_inference(inputs, batch_img_metas)
         return self.msfull_slide_inference(inputs, batch_img_metas)
 
-    def _resize_nchw(self, x, size):
+    def _resize_nchw(self, x, size, scale_factor=None):
         B, C, H, W = x.shape
         out = torch.empty(B, C, size[0], size[1], dtype=torch.float32, device=x.device)
-        ops.resize_bilinear(x, True, B, H, W, C, out, 1, tuple(size))
+        ops.resize_bilinear(x, True, B, H, W, C, out, 1, tuple(size), scale_factor=scale_factor)
         return out
 
     def lr_slide_inference(self, inputs, batch_img_metas):
         """:280-283: 0.5x bilinear input, the base class' sliding LinearHead pass, 2x bilinear logits."""
         B, _, H, W = inputs.shape
-        lh, lw = int(H * 0.5), int(W * 0.5)    # F.interpolate(scale_factor=0.5): floor(size * scale)
-        lr = self.slide_inference(self._resize_nchw(inputs, (lh, lw)), batch_img_metas)
-        return self._resize_nchw(lr, (int(lh * 2), int(lw * 2)))
+        lh, lw = int(H * 0.5), int(W * 0.5)    # F.interpolate(scale_factor=0.5): floor(size * scale), sampled at source scale 2
+        lr = self.slide_inference(self._resize_nchw(inputs, (lh, lw), scale_factor=0.5), batch_img_metas)
+        return self._resize_nchw(lr, (int(lh * 2), int(lw * 2)), scale_factor=2.0)
 
     # ---- coarse pass beside the window pass
     # When every window is refined whatever the coarse logits say (msfull_slide_inference; ms_slide_inference with a gate that cannot
@@ -559,11 +570,7 @@ class MsVFMEncoderDecoder(EncoderDecoder):
             if all_refined:          # (no gate to evaluate, no device->host sync)
                 refine = list(range(len(boxes)))
             else:
-                if len(boxes) <= 16:
-                    ops.conf_gate_windows(seg, [(y1, x1, y2 - y1, x2 - x1) for (y1, y2, x1, x2) in boxes], thr, cnt)
-                else:
-                    for j, (y1, y2, x1, x2) in enumerate(boxes):
-                        ops.conf_gate_count(seg, (y1, x1, y2 - y1, x2 - x1), thr, cnt[j:j + 1])
+                self._gate_counts(seg, boxes, thr, cnt)
                 fracs = [c / float(B * (b[1] - b[0]) * (b[3] - b[2])) for c, b in zip(cnt.tolist(), boxes)]
                 refine = [j for j, f in enumerate(fracs) if f < conf]
             hc, wc = boxes[0][1] - boxes[0][0], boxes[0][3] - boxes[0][2]
