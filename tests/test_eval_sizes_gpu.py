@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 import vfmseg_amd  # noqa: E402,F401
 from oracle.gen_golden import eval_sizes_probes, eval_sizes_seed  # noqa: E402
 from tests.helpers import full_state_dict, rel_err  # noqa: E402
+from tests.launch_replay import Recorder, describe, replay_attn_fwd, replay_gemm  # noqa: E402
 from vfmseg_amd import ops, presets  # noqa: E402
 from vfmseg_amd.precision import set_compute_dtype  # noqa: E402
 from vfmseg_amd.registry import MODELS  # noqa: E402
@@ -198,138 +199,25 @@ def test_gate_and_merge_over_eighteen_ragged_windows_against_float64():
 
 
 # ------------------------------------------------------------------------------------------------ GEMM / attention launch replay
-def _spec(t):
-    return None if t is None else (tuple(t.shape), tuple(t.stride()), t.dtype)
-
-
-def _same_storage(a, b):
-    return a is not None and b is not None and a.data_ptr() == b.data_ptr() and a.stride() == b.stride()
-
-
 def _record(model, G):
     """The distinct GEMM / attention launches (operand shapes, strides, dtypes, epilogue) of the bf16 predictions at every evaluation
     size: ms_slide_inference with every window refined (the largest token batches: 18 x 1025 rows) and with the golden's gate, and
-    lr_slide_inference.  Taken where ops builds the descriptors (gemm_desc serves ops.gemm and the launch plans alike)."""
-    gemms, attns = {}, {}
-    orig_g, orig_a = ops.gemm_desc, ops._attn_desc
-
-    def rec_g(a, b, c, *, alpha=1.0, bias=None, bias_mod=0, colscale=None, residual=None, ep_mode=ops.EP_NONE, aux=None, c2=None,
-              trans_a=False, trans_b=False, kb_rows=0, d=None):
-        key = (_spec(a), _spec(b), _spec(c), float(alpha), _spec(bias), int(bias_mod), _spec(colscale), _spec(residual),
-               _same_storage(residual, c), int(ep_mode), _spec(aux), _spec(c2), bool(trans_a), bool(trans_b), int(kb_rows))
-        gemms.setdefault(key, 0)
-        gemms[key] += 1
-        return orig_g(a, b, c, alpha=alpha, bias=bias, bias_mod=bias_mod, colscale=colscale, residual=residual, ep_mode=ep_mode, aux=aux,
-                      c2=c2, trans_a=trans_a, trans_b=trans_b, kb_rows=kb_rows, d=d)
-
-    def rec_a(q, k, v, o, B, H, d, nq_main, nq_extra, nk_main, nk_extra, scale, lse):
-        key = (_spec(q), _spec(k), _spec(v), _spec(o), B, H, d, nq_main, nq_extra, nk_main, nk_extra, float(scale), lse is not None)
-        attns.setdefault(key, 0)
-        attns[key] += 1
-        return orig_a(q, k, v, o, B, H, d, nq_main, nq_extra, nk_main, nk_extra, scale, lse)
-
-    ops.gemm_desc, ops._attn_desc = rec_g, rec_a
-    try:
+    lr_slide_inference.  Taken where ops builds the descriptors (tests/launch_replay.py: gemm_desc serves ops.gemm and the launch plans alike)."""
+    with Recorder() as rec:
         for h, w, mode, key in _cases(G):
             _predict(model, G, h, w, mode, key)
             if mode == "ms_slide_inference":
                 _predict(model, G, h, w, mode, key, conf=2.0)
         torch.cuda.synchronize()
-    finally:
-        ops.gemm_desc, ops._attn_desc = orig_g, orig_a
-    return gemms, attns
-
-
-def _fresh(spec, seed, scale=1.0):
-    """A tensor with the recorded shape / strides / dtype (padding columns of ld-padded views included), N(0, scale^2) values."""
-    shape, stride, dt = spec
-    t = torch.empty_strided(shape, stride, dtype=dt, device=DEV)
-    n = t.untyped_storage().nbytes() // t.element_size()
-    flat = torch.as_strided(t, (n,), (1,), 0)
-    flat.copy_(torch.randn(n, generator=torch.Generator(device=DEV).manual_seed(seed), device=DEV).mul_(scale).to(dt))
-    return t
-
-
-def _gelu_grad(x):
-    x = x.detach().clone().requires_grad_(True)
-    with torch.enable_grad():
-        F.gelu(x).sum().backward()
-    return x.grad
-
-
-def _replay_gemm(key, seed):
-    (sa, sb, sc, alpha, sbias, bias_mod, scs, sres, res_alias, ep, saux, sc2, ta, tb, kb) = key
-    assert ep in (ops.EP_NONE, ops.EP_GELU, ops.EP_RELU, ops.EP_MUL, ops.EP_MUL_GELU_GRAD), f"replay has no reference for ep_mode {ep}"
-    assert not kb and (len(sa[0]) == 2 or not (ta or tb)), key
-    a, b = _fresh(sa, seed, 0.5), _fresh(sb, seed + 1, 0.5)
-    c = _fresh(sc, seed + 2)
-    bias = _fresh(sbias, seed + 3) if sbias else None
-    cs = _fresh(scs, seed + 4) if scs else None
-    if res_alias:
-        res, res_val = c, c.double().clone()
-    else:
-        res = _fresh(sres, seed + 5) if sres else None
-        res_val = None if res is None else res.double()
-    aux = _fresh(saux, seed + 6) if saux else None
-    c2 = _fresh(sc2, seed + 7) if sc2 else None
-    aux_val = None if aux is None else aux.double()
-    ops.gemm(a, b, c, alpha=alpha, bias=bias, bias_mod=bias_mod, colscale=cs, residual=res, ep_mode=ep, aux=aux, c2=c2,
-             trans_a=ta, trans_b=tb)
-    ad = a.double().transpose(-1, -2) if ta else a.double()
-    bd = b.double() if tb else b.double().transpose(-1, -2)
-    v = alpha * torch.matmul(ad, bd)
-    if bias is not None:
-        n = v.shape[-1]
-        bm = bias_mod if bias_mod else n
-        v = v + bias.double()[torch.arange(n, device=DEV) % bm]
-    pre = v
-    if ep == ops.EP_GELU:
-        v = F.gelu(v)
-    elif ep == ops.EP_RELU:
-        v = F.relu(v)
-    elif ep == ops.EP_MUL:
-        v = v * aux_val
-    elif ep == ops.EP_MUL_GELU_GRAD:
-        v = v * _gelu_grad(aux_val)
-    if cs is not None:
-        v = v * cs.double()
-    if res_val is not None:
-        v = v + res_val
-    tol = 2e-5 if c.dtype == torch.float32 else 1e-2
-    err = _relerr(c, v)
-    assert err < tol, (key, err)
-    if c2 is not None:
-        assert _relerr(c2, pre) < (2e-5 if c2.dtype == torch.float32 else 1e-2), key
-    return err
-
-
-def _replay_attn(key, seed):
-    (sq, sk, sv, so, B, H, d, nq, nqe, nk, nke, scale, has_lse) = key
-    q, k, v = _fresh(sq, seed), _fresh(sk, seed + 1), _fresh(sv, seed + 2)
-    o = _fresh(so, seed + 3)
-    lse = torch.empty(B, H, nq + nqe, device=DEV) if has_lse else None
-    ops.attn_fwd(q, k, v, o, lse, B, H, d, nq, nqe, nk, nke, scale)
-
-    def gather(t, n, ne, b):   # image b -> [H, n + ne, d] float64
-        main = t[b * n:(b + 1) * n, :H * d].reshape(n, H, d)
-        if ne:
-            main = torch.cat([main, t[B * n + b:B * n + b + 1, :H * d].reshape(1, H, d)], 0)
-        return main.permute(1, 0, 2).double()
-
-    tol = 2e-5 if q.dtype == torch.float32 else 2e-2
-    worst = 0.0
-    for b in range(B):
-        qq, kk, vv = gather(q, nq, nqe, b), gather(k, nk, nke, b), gather(v, nk, nke, b)
-        ref = ((qq @ kk.transpose(-1, -2)) * scale).softmax(-1) @ vv
-        worst = max(worst, _relerr(gather(o, nq, nqe, b), ref))
-    assert worst < tol, (key, worst)
-    return worst
+    assert not any(rec.launches[k] for k in rec.launches if k not in ("gemm", "attn_fwd")), "a prediction issued a training-only launch"
+    return rec.launches["gemm"], rec.launches["attn_fwd"]
 
 
 def test_every_gemm_and_attention_launch_of_eval_size_predictions_against_float64(golden_dir, monkeypatch):
     """Every distinct GEMM and attention launch of the bf16 predictions at the evaluation sizes (the tile dispatcher's shape-exact rules
     choose by M: 18 windows = 18450 rows, 12 = 12300, 8 = 8200, plus the 2049-row coarse pass and the lr passes), replayed with fresh
-    operands of the same shapes, strides, dtypes and epilogue through the default dispatcher, against a float64 product on the device."""
+    operands of the same shapes, strides, dtypes and epilogue through the default dispatcher, against a float64 product on the device
+    (tests/launch_replay.py: operands scaled so that every epilogue term is visible, which the replay asserts from the reference alone)."""
     G = _golden(golden_dir)
     try:
         model = _model("bf16")
@@ -338,14 +226,12 @@ def test_every_gemm_and_attention_launch_of_eval_size_predictions_against_float6
         rows = sorted({k[2][0][-2] for k in gemms})
         assert 18 * 1025 in rows and 8 * 1025 in rows and 12 * 1025 in rows and 2049 in rows, rows
         for i, key in enumerate(sorted(gemms, key=repr)):
-            err = _replay_gemm(key, 1000 + 16 * i)
-            print(f"[replay gemm] A{key[0][0]}{'^T' if key[12] else ''} B{key[1][0]}{'^T' if key[13] else ''} -> C{key[2][0]} {key[2][2]} "
-                  f"ld(a,c)=({key[0][1][0]},{key[2][1][0]}) ep {key[9]} bias {key[4] is not None} colscale {key[6] is not None} "
-                  f"residual {key[7] is not None} c2 {key[11] is not None} x{gemms[key]}: rel err {err:.1e}")
+            res = replay_gemm(key, 1000 + 16 * i)     # asserts: fp32 output 2e-5, half output 1e-2 (C and C2), the mutant distances
+            print(f"{describe('gemm', key, gemms[key])}: rel err {res['c']:.1e}, mutant distances "
+                  + " ".join(f"{k} {v:.2f}" for k, v in res["mutants"].items()))
         for i, key in enumerate(sorted(attns, key=repr)):
-            err = _replay_attn(key, 5000 + 8 * i)
-            print(f"[replay attn] B {key[4]} H {key[5]} d {key[6]} nq {key[7]}+{key[8]} nk {key[9]}+{key[10]} {key[0][2]} "
-                  f"ld {key[0][1][0]} x{attns[key]}: rel err {err:.1e}")
+            res = replay_attn_fwd(key, 5000 + 8 * i)  # asserts: half 2e-2, fp32 2e-5
+            print(f"{describe('attn_fwd', key, attns[key])}: rel err {res['o']:.1e}")
         print(f"[replay] {len(gemms)} distinct GEMM launches, {len(attns)} distinct attention launches")
     finally:
         set_compute_dtype("bf16")

@@ -1193,3 +1193,52 @@ def test_gemm_bf16_tn_splitk(P, M, Q, ld):
     ops.gemm_splitk_tn(xs, y, slabs, kch)
     ref = xs.double().t() @ y.double()
     assert relerr(slabs.sum(0), ref) < 2e-5
+
+
+@pytest.mark.parametrize("L,M,valid,P,Q,ld,alpha", [(1, 4100, 4100, 64, 3072, 1088, 1.0), (3, 1100, 1025, 64, 1024, 1088, 0.5),
+                                                   (3, 300, 200, 32, 256, 40, 1.0), (1, 130, 70, 8, 64, 8, 2.0)])
+def test_gemm_bf16_tn_batched(L, M, valid, P, Q, ld, alpha):
+    """ops.gemm_tn_batched (one weight gradient per layer in one launch) against float64: out[l] = alpha * xs[l, :valid]^T @ y[l, :valid].
+    xs is a column slice of a wider buffer (P = 64 at ld 1088: the LoRA wgrad's T columns behind the 1024 activations); valid_rows
+    smaller than M and not a multiple of 64; the token rows past valid_rows hold NaN (the kernel reads them as zeros, by row index: the
+    64-row steps of problem l reach into them); alpha != 1."""
+    wide = rnd(L, M, ld, seed=71, scale=valid ** -0.25).bfloat16().to(DEV)
+    xs = wide[:, :, ld - P:]
+    y = rnd(L, M, Q, seed=72, scale=valid ** -0.25).bfloat16().to(DEV)
+    wide[:, valid:] = float("nan")
+    y[:, valid:] = float("nan")
+    out = torch.full((L, P, Q), float("nan"), device=DEV)
+    for rep in range(2):
+        ops.gemm_tn_batched(xs, y, out, valid, alpha=alpha)
+    assert torch.isfinite(out).all()
+    ref = alpha * torch.matmul(xs[:, :valid].double().transpose(1, 2), y[:, :valid].double())
+    assert relerr(out, ref) < 2e-5
+    assert alpha == 1.0 or relerr(ref / alpha, ref) > 1e-1     # a dropped alpha is visible
+
+
+@pytest.mark.parametrize("kch,P,Q,rows_used,sp,sq,alpha,accumulate", [
+    (13, 64, 1024, 32, 1024, 1, 1.0, True),      # LoRA dA [r, in] inside the flat buffer: rows_used < P
+    (13, 64, 3072, 32, 1, 32, 1.0, True),        # LoRA dB [out, r]: transposed destination (sp = 1, sq = r)
+    (16, 64, 1280, 32, 1280, 1, 0.25, True),     # alpha != 1
+    (4, 19, 256, 19, 256, 1, 1.0, False),        # overwrite
+    (2, 24, 100, 17, 1, 24, -1.5, False)])       # transposed, rows_used < P, row stride larger than rows_used: gaps stay untouched
+def test_slab_reduce(kch, P, Q, rows_used, sp, sq, alpha, accumulate):
+    """ops.slab_reduce (the split-K combine that adds straight into a parameter's slot of the flat gradient buffer) against float64:
+    dst[p*sp + q*sq] (+)= alpha * sum_k slabs[k, p, q] for p < rows_used; every other destination element bit-identical afterwards."""
+    slabs = rnd(kch, P, Q, seed=81).to(DEV)
+    n = (rows_used - 1) * sp + (Q - 1) * sq + 1 + 37
+    dst = rnd(n, seed=82).to(DEV)
+    before = dst.clone()
+    idx = (torch.arange(rows_used, device=DEV)[:, None] * sp + torch.arange(Q, device=DEV)[None, :] * sq).reshape(-1)
+    ops.slab_reduce(slabs, rows_used, dst, sp, sq, alpha=alpha, accumulate=accumulate)
+    touched = torch.zeros(n, dtype=torch.bool, device=DEV)
+    touched[idx] = True
+    assert torch.equal(dst[~touched], before[~touched])
+    ref = alpha * slabs.double().sum(0)[:rows_used].reshape(-1) + (before.double()[idx] if accumulate else 0.0)
+    plain = alpha * slabs.sum(0)[:rows_used].reshape(-1) + (before[idx] if accumulate else 0.0)
+    # bound: 4 x the error of the plain fp32 torch evaluation of the same sum against float64 on the same operands (summation order is the
+    # only freedom a correct kernel has); measured on these cases 5.7e-8 .. 1.1e-7, so the bound is 2.4e-7 .. 4.5e-7
+    # (floor: one fp32 rounding, 2^-24); the kernel itself 5.7e-8 .. 1.6e-7
+    e, e_plain = relerr(dst[idx], ref), relerr(plain, ref)
+    print(f"[slab_reduce kch {kch} P {P} Q {Q}] rel err {e:.2e}, plain fp32 evaluation {e_plain:.2e}")
+    assert e <= 4.0 * max(e_plain, 2.0 ** -24)
