@@ -267,6 +267,20 @@ int vfm_softmax_rows_bwd(const void* p, const float* dp, long ld_dp, void* ds, i
 int vfm_sam_attn_bwd_merge(const void* dqa, const void* dkT, const void* dvT, int dt, const float* rh, const float* rw, void* dqkv,
                            long ld, int nimg, int G, int S, int H, int d, int dp, int NP, int Dq, float scale, void* stream);
 
+/* ---- Rein adapter: token attention between the residual stream and the learnable tokens of a layer -------------
+ * (rein/models/backbones/reins.py:84-116, forward_delta_feat; its backward under autograd).  16-bit operands of the loaded library's
+ * half type; m = token_length <= 128, D % 128 == 0.  t / v: [128, D] row-major (ld = D), rows >= m zero, row 0 of v zero ("attend to
+ * nothing": column 0 of the softmax meets no value, reins.py:110-114); vt / tt: their transposes [D, 128] (ld = 128).
+ * vfm_rein_mix_fwd : P = softmax(c * x t^T) over the m real columns (pad columns: probability exactly 0), u = P v + x written in 16 bit
+ *                    (the A operand of the mlp_delta_f GEMM, reins.py:115).  x: fp32 stream rows (ld_x); optional outputs p [rows, 128]
+ *                    and x16 (the 16-bit copy of x the token gradient dT = dS^T x reads) - NULL at inference.
+ * vfm_rein_mix_bwd : dP = du v^T, dS = c * P * (dP - rowsum(P * dP)) written in 16 bit [rows, 128] (pad columns 0), and
+ *                    dx += du + dS t into the fp32 gradient stream. */
+int vfm_rein_mix_fwd(const float* x, long ld_x, const void* t, const void* vt, void* u, long ld_u, void* p, long ld_p, void* x16,
+                     long ld_x16, long rows, int D, int m, float c, void* stream);
+int vfm_rein_mix_bwd(const void* du, long ld_du, const void* p, long ld_p, const void* v, const void* tt, void* ds, long ld_ds,
+                     float* dx, long ld_dx, long rows, int D, int m, float c, void* stream);
+
 /* Flash-style forward of the same attention (inference; head dim 80 = SAM ViT-H): token-major qkv [nimg*G*G, 3*H*d] -> token-major
  * out [nimg*G*G, H*d] in ONE launch - windows of S = 14 on the zero-padded grid (padded tokens: k / v = projection bias) or global
  * attention (S = G = 32).  tbl_h / tbl_w: bf16 [2*SP, d] (SP = 16 for S = 14, 32 for S = 32) relative-index tables,

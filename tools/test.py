@@ -55,7 +55,7 @@ def main():
     model = MODELS.build(cfg["model"])
     sd = synth_like(model.state_dict())
     if a.checkpoint:
-        ck = torch.load(a.checkpoint, map_location="cpu")
+        ck = torch.load(a.checkpoint, map_location="cpu")   # (weights-only: Runner checkpoints keep their RNG states as tensors / numbers)
         sd.update(ck.get("state_dict", ck))
     if a.backbone:
         sd.update({"backbone." + k: v for k, v in torch.load(a.backbone, map_location="cpu").items()})

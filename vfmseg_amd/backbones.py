@@ -28,7 +28,10 @@ R_PAD = 64  # LoRA rank padded to one MFMA K-block
 # Data-parallel overlap (vfmseg_amd.parallel): the backbone backward is the last and longest autograd node, so it tells
 # the gradient synchroniser when buckets become final: "heads" when it starts (all decoder gradients are done) and
 # "lora" (with the block index just finished) as it walks the blocks from the last to the first.
-BACKWARD_EVENTS = {"heads_done": None, "block_done": None}
+BACKWARD_EVENTS = {"heads_done": None, "block_done": None, "backbone_done": None}
+# Backbone forward passes of the current step whose backward has not run yet.  Gradients shared by all layers (Rein) are final only when the
+# LAST of them has run - a segmentor may send the backbone over two inputs per step - so "backbone_done" fires when this returns to zero.
+_PENDING_BACKWARD = [0]
 
 
 # ------------------------------------------------------------------------------------------ parameter containers
@@ -136,6 +139,141 @@ class DinoVisionTransformer(nn.Module):
         b, d = x.shape[0], self.embed_dim
         v = xcat.view(b, hp, wp, len(self.out_indices), d)
         return tuple(v[:, :, :, i].permute(0, 3, 1, 2) for i in range(len(self.out_indices)))  # NCHW-shaped views
+
+
+@MODELS.register_module()
+class Reins(nn.Module):
+    """rein/models/backbones/reins.py:11-116: parameter container of the Rein adapter (same ctor kwargs, state_dict keys and initialisers).
+    The arithmetic is DinoEngine's (`_rein_forward` / `_rein_backward`).  On the HIP path: softmax attention, a learnable `scale`, and no
+    token-to-query link (the `rein_dinov2_linear.py` configs); `transform` / `merge` exist for the checkpoints' sake and never enter the graph."""
+
+    def __init__(self, num_layers, embed_dims, patch_size, query_dims=256, token_length=100, use_softmax=True, link_token_to_query=True,
+                 scale_init=0.001, zero_mlp_delta_f=False):
+        super().__init__()
+        if not use_softmax:
+            raise NotImplementedError("Reins(use_softmax=False): the HIP adapter kernels compute the softmax form (all reference configs)")
+        if zero_mlp_delta_f:
+            raise NotImplementedError("Reins(zero_mlp_delta_f=True) replaces the learnable scale by the constant 1: not on the HIP path")
+        if link_token_to_query:
+            raise NotImplementedError("Reins(link_token_to_query=True) feeds Mask2Former queries; the HIP path ships the linear-head configs "
+                                      "(link_token_to_query=False, rein_dinov2_linear.py:23)")
+        if token_length < 2:
+            raise ValueError("Reins: token_length must be at least 2 (token 0 is the 'attend to nothing' slot)")
+        self.num_layers, self.embed_dims, self.patch_size, self.query_dims = num_layers, embed_dims, patch_size, query_dims
+        self.token_length, self.link_token_to_query, self.scale_init = token_length, link_token_to_query, scale_init
+        self.use_softmax, self.zero_mlp_delta_f = use_softmax, zero_mlp_delta_f
+        self.create_model()
+
+    def create_model(self):
+        self.learnable_tokens = nn.Parameter(torch.empty([self.num_layers, self.token_length, self.embed_dims]))
+        self.scale = nn.Parameter(torch.tensor(self.scale_init))
+        self.mlp_token2feat = nn.Linear(self.embed_dims, self.embed_dims)
+        self.mlp_delta_f = nn.Linear(self.embed_dims, self.embed_dims)
+        val = math.sqrt(6.0 / float(3 * self.patch_size * self.patch_size + self.embed_dims))
+        nn.init.uniform_(self.learnable_tokens.data, -val, val)
+        nn.init.kaiming_uniform_(self.mlp_delta_f.weight, a=math.sqrt(5))
+        nn.init.kaiming_uniform_(self.mlp_token2feat.weight, a=math.sqrt(5))
+        self.transform = nn.Linear(self.embed_dims, self.query_dims)
+        self.merge = nn.Linear(self.query_dims * 3, self.query_dims)
+
+    def token_params(self):
+        return [self.learnable_tokens]
+
+    def live_params(self):
+        """The parameters the adapter step differentiates, in the order DinoEngine hands their gradients back."""
+        return self.token_params() + [self.mlp_token2feat.weight, self.mlp_token2feat.bias, self.mlp_delta_f.weight, self.mlp_delta_f.bias,
+                                      self.scale]
+
+    def inert_params(self):
+        return list(self.transform.parameters()) + list(self.merge.parameters())
+
+
+@MODELS.register_module()
+class LoRAReins(Reins):
+    """reins.py:119-148: the tokens of a layer are the product A_l [m, r] @ B_l [r, D]."""
+
+    def __init__(self, lora_dim=16, **kwargs):
+        self.lora_dim = lora_dim
+        super().__init__(**kwargs)
+
+    def create_model(self):
+        super().create_model()
+        del self.learnable_tokens
+        self.learnable_tokens_a = nn.Parameter(torch.empty([self.num_layers, self.token_length, self.lora_dim]))
+        self.learnable_tokens_b = nn.Parameter(torch.empty([self.num_layers, self.lora_dim, self.embed_dims]))
+        val = math.sqrt(6.0 / float(3 * self.patch_size * self.patch_size + (self.embed_dims * self.lora_dim) ** 0.5))
+        nn.init.uniform_(self.learnable_tokens_a.data, -val, val)
+        nn.init.uniform_(self.learnable_tokens_b.data, -val, val)
+
+    def token_params(self):
+        return [self.learnable_tokens_a, self.learnable_tokens_b]
+
+
+@MODELS.register_module()
+class ReinsDinoVisionTransformer(DinoVisionTransformer):
+    """rein/models/backbones/reins_dinov2.py:7-49: a frozen DINOv2 whose every block is followed by the Rein adapter step on the patch
+    tokens (the class token passes through); the taps are taken after the adapter."""
+
+    def __init__(self, reins_config=None, init_cfg=None, **kwargs):
+        super().__init__(**kwargs)
+        self.reins = MODELS.build(reins_config)
+        if self.reins.num_layers != self.n_blocks or self.reins.embed_dims != self.embed_dim:
+            raise ValueError("reins_config: num_layers / embed_dims must equal the backbone's depth / embed_dim")
+        self._rein_train = False
+        # rein_dinov2_linear.py:38-41: the frozen base arrives through init_cfg=dict(type="Pretrained", checkpoint=PATH)
+        self.pretrained = None
+        ck = init_cfg.get("checkpoint") if isinstance(init_cfg, dict) else None
+        if ck is not None:
+            if init_cfg.get("type", "Pretrained") != "Pretrained":
+                raise NotImplementedError(f"init_cfg type {init_cfg.get('type')!r}: only dict(type='Pretrained', checkpoint=...) is read")
+            self.load_pretrained_base(ck)
+
+    def load_pretrained_base(self, checkpoint):
+        """The frozen DINOv2 weights (bare keys: cls_token, pos_embed, patch_embed.*, blocks.N.*, ...) from a path or a state dict.  Every
+        base parameter must be in it - a file whose keys do not match (a wrong prefix) is an error, not a silently untrained base; the
+        `reins.*` keys may be absent (they come from the adapter's own checkpoint or its initialisers)."""
+        sd = torch.load(checkpoint, map_location="cpu") if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
+        sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+        missing, _ = self.load_state_dict(sd, strict=False)
+        missing = [k for k in missing if not k.startswith("reins.")]
+        if missing:
+            raise RuntimeError(f"pretrained backbone {checkpoint if isinstance(checkpoint, (str, os.PathLike)) else '<state dict>'}: "
+                               f"{len(missing)} base parameters not found (first: {missing[:3]}; the file holds e.g. {list(sd)[:3]})")
+        self.pretrained = checkpoint if isinstance(checkpoint, (str, os.PathLike)) else "<state dict>"
+        self.engine().invalidate()
+
+    def train(self, mode=True):
+        """reins_dinov2.py:36-40 + utils.py:9-58: only parameters whose name contains 'reins' are trainable and only the `reins` module is
+        in train mode.  `transform` / `merge` never enter the graph (link_token_to_query=False): they stay frozen, like the inert EVA02
+        adapters of LoRABackbone.train - torch's AdamW would skip their missing gradients, the flat-buffer optimiser must not decay them."""
+        nn.Module.train(self, False)
+        self._rein_train = bool(mode)
+        if mode:
+            for n, p in self.named_parameters():
+                p.requires_grad = "reins" in n
+            for p in self.reins.inert_params():
+                p.requires_grad = False
+            self.reins.train(True)
+        return self
+
+    def adapter_training(self):
+        return self._rein_train
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        """reins_dinov2.py:42-49: only the keys that contain 'rein' are kept (the frozen base comes from its own checkpoint)."""
+        if args:   # torch's deprecated positional form (destination, prefix, keep_vars)
+            args = list(args) + [None] * (3 - len(args))
+            destination, prefix, keep_vars = args[0], args[1] or "", bool(args[2])
+        state = super().state_dict(destination=destination, prefix=prefix, keep_vars=keep_vars)
+        for k in [k for k in state.keys() if k.startswith(prefix) and "rein" not in k[len(prefix):]]:
+            state.pop(k)
+        return state
+
+    def forward(self, x):
+        xcat, (hp, wp) = self.forward_tokens([(x, None)], training=self._rein_train)
+        b, d = x.shape[0], self.embed_dim
+        v = xcat.view(b, hp, wp, len(self.out_indices), d)
+        return tuple(v[:, :, :, i].permute(0, 3, 1, 2) for i in range(len(self.out_indices)))
 
 
 class _Holder(nn.Module):
@@ -413,11 +551,16 @@ class DinoEngine:
     def lora_on(self):
         return isinstance(self.vit.blocks[0].attn.qkv, LoraLinear)
 
+    def rein_on(self):
+        return getattr(self.vit, "reins", None) is not None
+
     def trainable(self):
         out = []
         if self.lora_on():
             for blk in self.vit.blocks:
                 out += [blk.attn.qkv.lora_A["default"].weight, blk.attn.qkv.lora_B["default"].weight]
+        if self.rein_on():   # (after the per-block LoRA factors: backward() returns its gradients in this order)
+            out += self.vit.reins.live_params()
         return out
 
     # ---- frozen weights, packed once per (dtype, device)
@@ -524,6 +667,7 @@ class DinoEngine:
         dev = P["dev"]
         D, H, ps = v.embed_dim, v.num_heads, v.patch_size
         lora = self.lora_on()
+        rein = self._rein_pack(P) if self.rein_on() else None
         merged = None
         from .precision import split3 as _x3_mode
         x3 = _x3_mode() and not is_half(cd)
@@ -621,7 +765,7 @@ class DinoEngine:
             ops.layernorm_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2, split_out=so)
             hid = Lp["fc1"].n
             g = ops.empty_ld(M, hid, cd, dev)
-            if training and lora:   # the forward also saves gelu'(pre-activation): what fc2's dgrad multiplies by (mlp.py:34-40)
+            if training and (lora or (rein is not None and need_grad)):   # the forward also saves gelu'(pre-activation): what fc2's dgrad multiplies by (mlp.py:34-40)
                 hpre = torch.empty(M, hid, dtype=cd, device=dev)
                 Lp["fc1"].fwd(a2, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU_DGELU, c2=hpre)
             else:
@@ -632,17 +776,19 @@ class DinoEngine:
             S.update(a1=a1, st1=st1, qkv=qkv, ao=ao, lse=lse, x_mid=xm, a2=a2, st2=st2, hpre=hpre, g=g)
             saved.append(S)
             x = xo
+            if rein is not None:   # the adapter step on the patch rows; the taps below read its output (reins_dinov2.py:22-33)
+                x = self._rein_forward(rein, li, x, Mp, S if (training and need_grad) else None)
             for i, oi in enumerate(v.out_indices):   # (an index may be listed more than once: every copy is a tap of its own)
                 if oi == li:
                     ops.cast(x[:Mp], xcat[:, i * D:(i + 1) * D])
-        ctx = dict(saved=saved, nimg=nimg, Np=Np, M=M, Mp=Mp, P=P, training=training, A1all=A1all, XDall=XDall)
+        ctx = dict(saved=saved, nimg=nimg, Np=Np, M=M, Mp=Mp, P=P, training=training, A1all=A1all, XDall=XDall, rein=rein)
         return xcat, (hp, wp), ctx
 
     def _train_plan(self, P, nimg, Np, training, merged):
         """The launch plan of this call's shape when the call is the hot one (training with gradients, LoRA with dropout on every
         block, 16-bit mode, weight gradients into the optimiser's flat buffer) and no earlier forward still owns the plan's buffers."""
         v = self.vit
-        if (not training or merged is not None or not self.lora_on() or not is_half(P["cd"])
+        if (not training or merged is not None or not self.lora_on() or self.rein_on() or not is_half(P["cd"])
                 or os.environ.get("VFMSEG_PLAN", "1") == "0" or v.embed_dim % 256 != 0):
             return None
         q0 = v.blocks[0].attn.qkv
@@ -673,8 +819,10 @@ class DinoEngine:
         scale = hd ** -0.5
         M, Mp, nimg, Np = ctx["M"], ctx["Mp"], ctx["nimg"], ctx["Np"]
         dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
-        grads = [None] * (2 * len(v.blocks))
+        grads = [None] * (2 * len(v.blocks) if self.lora_on() else 0)
         nL = len(v.blocks)
+        rein = ctx.get("rein")
+        rein_acc = self._rein_backward_begin(rein) if rein is not None else None
         # LoRA weight gradients, layer-batched: dB_l^T = T_l^T dqkv_l and dA_l = s dT_l^T drop(LN x)_l are 2 x 24 skinny GEMMs
         # (64 output rows, reduction over the 4100 tokens) that each needed split-K slabs + a combine launch (35 us per layer for
         # 0.3 % of the step's FLOPs).  Keeping dqkv / d[LN x | T] of the layers (0.8 GB of 288) turns them into TWO batched GEMMs
@@ -691,6 +839,9 @@ class DinoEngine:
             DQKVall = torch.empty(nL, M, 3 * D, dtype=cd, device=dev)
         half = nL // 2
         fuse_t = is_half(cd) and D % 256 == 0  # LN backward emits the next dgrad operand bf16(dx * gamma) itself
+        # with an adapter between block li-1 and li the tap gradient belongs to the adapter's OUTPUT and the adapter's backward rewrites dx
+        # before t = bf16(dx * g2) may be formed: the LN1 backward then must not emit t for the block below
+        fuse_t1 = fuse_t and rein is None
         def add_tap(li):
             for i, oi in enumerate(v.out_indices):
                 if oi == li:
@@ -703,6 +854,8 @@ class DinoEngine:
             # ---- MLP branch: x_out = x_mid + g2 * fc2(gelu(fc1(LN2(x_mid))))
             if t is None:  # (the previous iteration's LN1 backward already produced t = bf16(dx * g2) otherwise)
                 add_tap(li)
+                if rein is not None:
+                    self._rein_backward(rein, rein_acc, li, dx, Mp, S)
                 t = torch.empty(M, D, dtype=cd, device=dev)
                 ops.cast(dx, t, Lp["g2"])
             hid = Lp["fc1"].n
@@ -761,7 +914,7 @@ class DinoEngine:
                 # d LN1(x) = da1[:, :D] + mask * (s * dT @ A)
                 ep = dict(ep_mode=ops.EP_MUL, aux=S["mask"]) if S["mask"] is not None else {}
                 ops.gemm(da1[:, D:D + R_PAD], Lp["at"], da1[:, :D], alpha=q.scaling, residual=da1[:, :D], **ep)
-            if fuse_t and li > 0:  # dx becomes d(x_out) of block li-1: its tap gradient goes in first, then LN1 backward
+            if fuse_t1 and li > 0:  # dx becomes d(x_out) of block li-1: its tap gradient goes in first, then LN1 backward
                 add_tap(li - 1)     # accumulates and emits t = bf16(dx * g2[li-1]) for that block's fc2 dgrad
                 ops.layernorm_bwd_scaled(da1[:, :D], S["x_in"], Lp["n1w"], S["st1"], dx, t, P["layers"][li - 1]["g2"],
                                          accumulate_dx=True)
@@ -778,7 +931,192 @@ class DinoEngine:
                             BACKWARD_EVENTS["block_done"](lj)
             elif BACKWARD_EVENTS["block_done"] is not None:
                 BACKWARD_EVENTS["block_done"](li)
+        if rein is not None:
+            grads += self._rein_backward_end(rein, rein_acc)
         return grads
+
+    # ---- Rein adapter (reins.py:84-116): x' = x + scale * mlp_delta_f(softmax(c x T^T)[:, 1:] V + x) on the patch rows
+    def _rein_fused(self, P):
+        """The token attention of the adapter step has two forms with the same arithmetic: the composed one (ops.gemm + ops.softmax_rows +
+        ops.cast: the project's tuned GEMMs, four launches per direction) and the fused kernels (vfm_rein_mix_fwd / _bwd: one launch, the score and
+        probability maps never leave the chip).  VFMSEG_REIN_FUSED=1 selects the fused kernels in the 16-bit modes for the shapes they cover
+        (D % 256 == 0, token_length <= 128); the default is the composed form, which measures faster in both directions at 2048 and at
+        9216 rows - the exact-fp32 and split-bf16 modes always take it (ops.gemm gives their products)."""
+        r = self.vit.reins
+        return (is_half(P["cd"]) and os.environ.get("VFMSEG_REIN_FUSED", "0") == "1" and self.vit.embed_dim % 256 == 0
+                and r.token_length <= ops.REIN_TOK)
+
+    def _rein_pack(self, P):
+        """Per forward call (the parameters move every optimiser step): the tokens T_l = A_l B_l and the values V_l = T_l[1:] W_t2f^T + b of
+        ALL layers as [L, TP, D] operands in the compute dtype with zero pad rows (V with a zero row 0: column 0 of the softmax attends to
+        nothing), their transposes for the fused kernels, mlp_delta_f packed, and `scale` spread over a D-vector for the GEMM epilogue."""
+        from .optim import PARAM_EPOCH
+        r = self.vit.reins
+        cd, dev = P["cd"], P["dev"]
+        D, nL, m = self.vit.embed_dim, r.num_layers, r.token_length
+        live = r.live_params()
+        key = (PARAM_EPOCH[0], self._rein_fused(P)) + tuple(x for p_ in live for x in (p_._version, p_.data_ptr()))
+        R = P.get("rein")
+        if R is not None and R["key"] == key:
+            return R
+        TP = (max(m, ops.REIN_TOK) + 63) // 64 * 64
+        if R is None or R["TP"] != TP:
+            z = lambda *sh, dt=cd: torch.zeros(*sh, dtype=dt, device=dev)   # noqa: E731  (pad rows are written once, here)
+            R = P["rein"] = dict(TP=TP, T32=z(nL, TP, D, dt=torch.float32), T=z(nL, TP, D), V=z(nL, TP, D), TT=None, VT=None,
+                                 scalevec=torch.empty(D, dtype=torch.float32, device=dev))
+        R["key"], R["m"], R["c"], R["fused"] = key, m, float(D) ** -0.5, self._rein_fused(P)
+        with torch.no_grad():
+            T32 = R["T32"]
+            toks = [p_.detach() for p_ in r.token_params()]
+            if len(toks) == 2:   # LoRAReins: T_l = A_l @ B_l (exact fp32, K = lora_dim)
+                ops.gemm(toks[0], toks[1], T32[:, :m], trans_b=True)
+            else:
+                ops.strided_copy(toks[0], T32, (nL, m, D), (m * D, D, 1), (TP * D, D, 1))
+            if cd != torch.float32:
+                ops.cast(T32.view(nL * TP, D), R["T"].view(nL * TP, D))
+            else:
+                R["T"] = T32
+            Wt, Wd = r.mlp_token2feat, r.mlp_delta_f
+            R["wt"], R["wd"] = Packed(Wt.weight.detach(), cd), Packed(Wd.weight.detach(), cd)
+            R["bt"], R["bd"] = Wt.bias.detach(), Wd.bias.detach()
+            vtmp = torch.empty(nL * TP, D, dtype=torch.float32, device=dev)
+            R["wt"].fwd(R["T"].view(nL * TP, D), vtmp, bias=R["bt"])
+            vt3 = vtmp.view(nL, TP, D)
+            ops.strided_copy(vt3[:, 1:m], R["V"][:, 1:m], (nL, m - 1, D), (TP * D, D, 1), (TP * D, D, 1))
+            if R["fused"]:
+                if R["TT"] is None:
+                    R["TT"], R["VT"] = torch.zeros(nL, D, TP, dtype=cd, device=dev), torch.zeros(nL, D, TP, dtype=cd, device=dev)
+                ops.strided_copy(T32, R["TT"], (nL, D, m), (TP * D, 1, D), (D * TP, TP, 1))
+                ops.strided_copy(vt3[:, 1:m], R["VT"][:, :, 1:m], (nL, D, m - 1), (TP * D, 1, D), (D * TP, TP, 1))
+            ops.strided_copy(r.scale.detach().reshape(1), R["scalevec"], (D,), (0,), (1,))
+        return R
+
+    def _rein_forward(self, R, li, x, Mp, S):
+        """x [M, D] fp32 stream after block li -> the stream after the adapter.  S (training with gradients): the dict backward reads; the
+        stream is then NOT updated in place (the block's own backward and the token gradient dT = dS^T x read the pre-adapter rows)."""
+        cd, dev = R["T"].dtype, x.device
+        D, m, TP = x.shape[1], R["m"], R["TP"]
+        xp = x[:Mp]
+        u = torch.empty(Mp, D, dtype=cd, device=dev)
+        p = torch.empty(Mp, TP, dtype=cd, device=dev) if S is not None else None
+        x16 = None
+        if R["fused"]:
+            x16 = torch.empty(Mp, D, dtype=cd, device=dev) if S is not None else None
+            ops.rein_mix_fwd(xp, R["T"][li], R["VT"][li], u, m, R["c"], p=p, x16=x16)
+        else:
+            if cd != torch.float32:
+                x16 = torch.empty(Mp, D, dtype=cd, device=dev)
+                ops.cast(xp, x16)
+            sc = torch.empty(Mp, TP, dtype=torch.float32, device=dev)
+            ops.gemm(x16 if x16 is not None else xp, R["T"][li], sc, alpha=R["c"])
+            if p is None:
+                p = torch.empty(Mp, TP, dtype=cd, device=dev)
+            ops.softmax_rows(sc, p, m)
+            ops.gemm(p, R["V"][li], u, residual=xp, trans_b=True)
+        if S is None:
+            xn = x     # nothing reads the pre-adapter rows again: the epilogue's residual is its own destination
+        else:
+            xn = torch.empty_like(x)
+            ops.cast(x[Mp:], xn[Mp:])   # the class tokens pass through
+            S.update(rein_u=u, rein_p=p, rein_x=x16 if x16 is not None else xp)
+        R["wd"].fwd(u, xn[:Mp], bias=R["bd"], colscale=R["scalevec"], residual=xp)
+        return xn
+
+    def _rein_backward_begin(self, R):
+        dev = R["T"].device
+        nL, TP, D = R["T"].shape
+        z = lambda *sh: torch.zeros(*sh, dtype=torch.float32, device=dev)   # noqa: E731
+        return dict(dT=z(nL, TP, D), dV=z(nL, TP, D), Gm=z(D, D), gb=z(D))
+
+    @staticmethod
+    def _tn(xs, y, out, alpha=1.0, accumulate=False):
+        """out[P, Q] (+)= alpha * xs^T @ y over the token rows, both operands consumed token-major."""
+        if is_half(xs.dtype):
+            ops.gemm_tn_batched(xs.unsqueeze(0), y.unsqueeze(0), out.unsqueeze(0), xs.shape[0], alpha=alpha, accumulate=accumulate)
+        else:
+            ops.gemm(xs, y, out, alpha=alpha, residual=out if accumulate else None, trans_a=True, trans_b=True)
+
+    def _rein_backward(self, R, acc, li, dx, Mp, S):
+        """dx[:Mp] holds d x' of layer li's adapter (tap gradient included) and becomes d x; the token / value gradients of the layer and
+        the running sums of the shared mlp_delta_f gradients go to `acc` (ISSUE formulas: reins.py:84-116 under autograd)."""
+        cd, dev = R["T"].dtype, dx.device
+        D, m, TP, c = dx.shape[1], R["m"], R["TP"], R["c"]
+        u, p, xs = S["rein_u"], S["rein_p"], S["rein_x"]
+        g = torch.empty(Mp, D, dtype=cd, device=dev)
+        ops.cast(dx[:Mp], g)
+        # shared mlp_delta_f: Gm += g^T u and gb += colsum(g) (the learnable scale multiplies them at the end, and gives dscale)
+        self._tn(g, u, acc["Gm"], accumulate=True)
+        ops.colsum(g, acc["gb"], accumulate=True)
+        du = torch.empty(Mp, D, dtype=cd, device=dev)
+        R["wd"].dgrad(g, du, colscale=R["scalevec"])          # du = (scale g) W_d
+        ds = torch.empty(Mp, TP, dtype=cd, device=dev)
+        if R["fused"]:
+            ops.rein_mix_bwd(du, p, R["V"][li], R["TT"][li], ds, dx[:Mp], m, c)
+            a = 1.0
+        else:
+            dp = torch.empty(Mp, TP, dtype=torch.float32, device=dev)
+            ops.gemm(du, R["V"][li], dp)                        # column 0 and the pad columns meet zero rows of V
+            ops.softmax_rows_bwd(p, dp, ds, m, 1, 1)
+            ops.gemm(ds, R["T"][li], dx[:Mp], alpha=c, residual=dx[:Mp], trans_b=True)
+            ops.strided_copy(du, dx[:Mp], (Mp, D), (du.stride(0), 1), (dx.stride(0), 1), accumulate=True)
+            a = c
+        self._tn(ds, xs, acc["dT"][li], alpha=a)               # dT = dS^T x
+        self._tn(p, du, acc["dV"][li])                         # dV = P^T du (row 0 is dropped at the end)
+        S["rein_u"] = S["rein_p"] = S["rein_x"] = None
+
+    def _rein_backward_end(self, R, acc):
+        """The layer-batched tail: dT[1:] += dV W_t2f, the token-factor gradients, mlp_token2feat's and mlp_delta_f's gradients, dscale.
+        Gradients go straight into the optimiser's flat buffer where it exposes one (None is handed to autograd then)."""
+        from .functional import direct_grad_target
+        r = self.vit.reins
+        cd, dev = R["T"].dtype, R["T"].device
+        nL, TP, D = R["T"].shape
+        m = R["m"]
+        z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=dev)   # noqa: E731
+        # dV with row 0 and the pad rows dropped, in the compute dtype
+        dvz = z(nL, TP, D, dt=cd)
+        ops.strided_copy(acc["dV"][:, 1:m], dvz[:, 1:m], (nL, m - 1, D), (TP * D, D, 1), (TP * D, D, 1))
+        dvz2, T2 = dvz.view(nL * TP, D), R["T"].view(nL * TP, D)
+        gWt, gbt = z(D, D), z(D)
+        self._tn(dvz2, T2, gWt)                                 # dW_t2f = dV^T T[1:] (row 0 of dvz is zero)
+        ops.colsum(dvz2, gbt)
+        back = torch.empty(nL * TP, D, dtype=torch.float32, device=dev)
+        R["wt"].dgrad(dvz2, back)                               # dV W_t2f
+        dT = acc["dT"]
+        ops.strided_copy(back.view(nL, TP, D)[:, 1:m], dT[:, 1:m], (nL, m - 1, D), (TP * D, D, 1), (TP * D, D, 1), accumulate=True)
+        toks = r.token_params()
+        if len(toks) == 2:
+            A, Bm = toks[0].detach(), toks[1].detach()
+            gA, gB = torch.empty_like(A), torch.empty_like(Bm)
+            ops.gemm(dT[:, :m], Bm, gA)                          # dA_l = dT_l B_l^T
+            ops.gemm(A, dT[:, :m], gB, trans_a=True, trans_b=True)   # dB_l = A_l^T dT_l
+            gtok = [gA, gB]
+        else:
+            gt = torch.empty_like(toks[0])
+            ops.strided_copy(dT, gt, (nL, m, D), (TP * D, D, 1), (m * D, D, 1))
+            gtok = [gt]
+        # dscale = <sum_l g^T u, W_d> + <sum_l colsum g, b_d>; then dW_d = scale * Gm, db_d = scale * gb
+        Gm, gb = acc["Gm"], acc["gb"]
+        prod = torch.empty(D, D, dtype=torch.float32, device=dev)
+        ops.mul_mask(Gm, r.mlp_delta_f.weight.detach(), prod)
+        part = torch.empty(D, dtype=torch.float32, device=dev)
+        ops.colsum(prod, part)
+        pb = torch.empty(1, D, dtype=torch.float32, device=dev)
+        ops.mul_mask(gb.view(1, D), R["bd"].view(1, D), pb)
+        ops.axpby(pb.view(-1), 1.0, part, 1.0)
+        gscale = z(1)
+        ops.colsum(part.view(D, 1), gscale)
+        ops.scale_by_device_scalar(Gm.view(-1), r.scale.detach())
+        ops.scale_by_device_scalar(gb, r.scale.detach())
+        out = []
+        for p_, g_ in zip(r.live_params(), gtok + [gWt, gbt, Gm, gb, gscale.view(())]):
+            tgt = direct_grad_target(p_)
+            if tgt is not None:
+                ops.axpby(g_.reshape(-1), 1.0, tgt.view(-1), 1.0)
+                out.append(None)
+            else:
+                out.append(g_)
+        return out
 
     def _lora_wgrads_batched(self, P, ctx, DA1all, DQKVall, lo, hi, M, D):
         """LoRA weight gradients of layers [lo, hi): two batched TN GEMMs + one batched scatter-accumulate into the flat buffer."""
@@ -903,6 +1241,7 @@ class _BackboneFn(torch.autograd.Function):
                 xcat, grid, c = eng.forward(jobs, training, seed)
         if need_grad:
             ctx.eng, ctx.c = eng, c
+            _PENDING_BACKWARD[0] += 1
         else:
             c["saved"] = None
         ctx.nparams = len(lora_params)
@@ -913,6 +1252,7 @@ class _BackboneFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dxcat, _):
+        _PENDING_BACKWARD[0] = max(_PENDING_BACKWARD[0] - 1, 0)
         if dxcat is None:
             return (None, None, None, None) + (None,) * ctx.nparams
         if BACKWARD_EVENTS["heads_done"] is not None:
@@ -921,6 +1261,8 @@ class _BackboneFn(torch.autograd.Function):
             BACKWARD_EVENTS["heads_done"]()
         with ops.region("backbone"):
             grads = ctx.eng.backward(ctx.c, dxcat.contiguous())
+        if BACKWARD_EVENTS.get("backbone_done") is not None and _PENDING_BACKWARD[0] == 0:
+            BACKWARD_EVENTS["backbone_done"]()    # gradients shared by all layers (Rein) are complete only now
         return (None, None, None, None) + tuple(grads)
 
 

@@ -145,6 +145,8 @@ SIGNATURES = {
     "vfm_sam_attn_bwd_prep": [vp, cl, vp, cl, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp],
     "vfm_softmax_rows_batched": [vp, cl, vp, ci, cl, cl, ci, ci, ci, ci, vp],
     "vfm_softmax_rows_bwd": [vp, vp, cl, vp, ci, cl, cl, ci, ci, ci, ci, vp],
+    "vfm_rein_mix_fwd": [vp, cl, vp, vp, vp, cl, vp, cl, vp, cl, cl, ci, ci, cf, vp],
+    "vfm_rein_mix_bwd": [vp, cl, vp, cl, vp, vp, vp, cl, vp, cl, cl, ci, ci, cf, vp],
     "vfm_sam_attn_bwd_merge": [vp, vp, vp, ci, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp],
     "vfm_sam_attn_flash_fwd": [vp, cl, vp, vp, vp, vp, cl, ci, ci, ci, ci, ci, cf, vp],
     "vfm_sam_attn_flash_fwd_train": [vp, cl, vp, vp, vp, vp, cl, ci, ci, ci, ci, ci, cf, vp, vp, vp],

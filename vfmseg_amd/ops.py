@@ -674,9 +674,10 @@ def gemm_splitk_tn(xs, y, slabs, kch):
     return slabs
 
 
-def gemm_tn_batched(xs, y, out, valid_rows, alpha=1.0):
+def gemm_tn_batched(xs, y, out, valid_rows, alpha=1.0, accumulate=False):
     """out[l] = alpha * xs[l]^T @ y[l] for independent problems l (one weight gradient per layer in ONE launch): xs [L, M, P],
-    y [L, M, Q] bf16 views (unit column stride, P % 8 == 0, Q % 8 == 0), out fp32 [L, P, Q]; token rows >= valid_rows read as zeros."""
+    y [L, M, Q] bf16 views (unit column stride, P % 8 == 0, Q % 8 == 0), out fp32 [L, P, Q]; token rows >= valid_rows read as zeros.
+    accumulate: out[l] += ... (the epilogue's residual is its own destination)."""
     lib = L.load()
     d = L.GemmDesc()
     Lb, M, P = xs.shape
@@ -691,6 +692,8 @@ def gemm_tn_batched(xs, y, out, valid_rows, alpha=1.0):
     d.alpha = float(alpha)
     d.batch, d.stride_a, d.stride_b, d.stride_c = Lb, xs.stride(0), y.stride(0), P * Q
     d.kb_rows = -int(valid_rows)
+    if accumulate:
+        d.residual, d.r_dt, d.ldr = L.ptr(out), L.dt_of(out), Q
     fin = PROFILE("gemm_tn", 2.0 * P * Q * valid_rows * Lb, REGION[-1]) if PROFILE is not None else None
     L.check(lib.vfm_gemm(C.byref(d), L.stream()), "vfm_gemm")
     if fin is not None:
@@ -909,6 +912,36 @@ def softmax_rows(scores2d, out2d, n):
     L.check(lib.vfm_softmax_rows(L.ptr(scores2d), _ld(scores2d), L.ptr(out2d), L.dt_of(out2d), _ld(out2d), scores2d.shape[0], n,
                                  out2d.shape[1], L.stream()), "vfm_softmax_rows")
     return out2d
+
+
+REIN_TOK = 128   # token columns of the fused Rein kernels (token_length padded)
+
+
+def rein_mix_fwd(x, t, vt, u, m, c, p=None, x16=None):
+    """Rein token attention, forward (vfm_rein_mix_fwd): x fp32 [rows, D] (row-strided view), t [128, D] / vt [D, 128] 16-bit contiguous
+    (zero pad rows, zero row 0 of v), u [rows, D] 16-bit = softmax(c x t^T) v + x; optional p [rows, 128] and x16 [rows, D] for backward."""
+    lib = L.load()
+    rows, D = x.shape
+    assert x.dtype == torch.float32 and t.shape == (REIN_TOK, D) and vt.shape == (D, REIN_TOK) and t.is_contiguous() and vt.is_contiguous()
+    assert is_half(u.dtype) and u.shape == (rows, D) and t.dtype == vt.dtype == u.dtype
+    assert p is None or (p.shape == (rows, REIN_TOK) and p.dtype == u.dtype)
+    assert x16 is None or (x16.shape == (rows, D) and x16.dtype == u.dtype)
+    L.check(lib.vfm_rein_mix_fwd(L.ptr(x), _ld(x), L.ptr(t), L.ptr(vt), L.ptr(u), _ld(u), L.ptr(p), _ld(p) if p is not None else 0, L.ptr(x16),
+                                 _ld(x16) if x16 is not None else 0, rows, D, int(m), float(c), L.stream()), "vfm_rein_mix_fwd")
+    return u
+
+
+def rein_mix_bwd(du, p, v, tt, ds, dx, m, c):
+    """Rein token attention, backward (vfm_rein_mix_bwd): du [rows, D], p [rows, 128], v [128, D], tt [D, 128] 16-bit; writes ds [rows, 128]
+    16-bit and accumulates dx (fp32 [rows, D] row-strided view) += du + ds t."""
+    lib = L.load()
+    rows, D = du.shape
+    assert is_half(du.dtype) and p.dtype == v.dtype == tt.dtype == ds.dtype == du.dtype and dx.dtype == torch.float32
+    assert v.shape == (REIN_TOK, D) and tt.shape == (D, REIN_TOK) and v.is_contiguous() and tt.is_contiguous()
+    assert p.shape == (rows, REIN_TOK) and ds.shape == (rows, REIN_TOK) and dx.shape == (rows, D)
+    L.check(lib.vfm_rein_mix_bwd(L.ptr(du), _ld(du), L.ptr(p), _ld(p), L.ptr(v), L.ptr(tt), L.ptr(ds), _ld(ds), L.ptr(dx), _ld(dx), rows, D,
+                                 int(m), float(c), L.stream()), "vfm_rein_mix_bwd")
+    return dx
 
 
 def sam_attn_merge(o_win, out, nimg, G, S, H, d):

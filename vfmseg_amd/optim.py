@@ -55,9 +55,23 @@ def param_options(model, base_lr, base_wd, paramwise_cfg):
     return out
 
 
+def is_rein_name(n):
+    return n.startswith("reins.") or ".reins." in n
+
+
+def grad_group(n):
+    """Which bucket family a parameter's gradient belongs to (see production_order)."""
+    if is_rein_name(n):
+        return "reins"
+    return "lora" if "lora_" in n else ("aux_decoder" if n.startswith("aux_decoder") else "decode_head")
+
+
 def production_order(names):
-    """Gradient-production order of backward: aux_decoder, decode_head, then LoRA blocks from the last to the first."""
+    """Gradient-production order of backward: aux_decoder, decode_head, then LoRA blocks from the last to the first, then the Rein adapter
+    (`backbone.reins.*`: weights shared by all layers, whose gradients are complete only when the backbone backward ends)."""
     def key(n):
+        if is_rein_name(n):
+            return (3, 0, n)
         if "lora_" in n:
             try:
                 blk = int(n.split("blocks.")[1].split(".")[0])
@@ -121,10 +135,10 @@ class FusedAdamW:
         self.param_groups = [dict(lr=lr)]
 
     def bucket_slices(self):
-        """[(name, start, end)] contiguous gradient slices in production order: aux_decoder, decode_head, lora."""
+        """[(name, start, end)] contiguous gradient slices in production order: aux_decoder, decode_head, lora, reins."""
         cuts, cur = [], None
         for nm, a in zip(self.names, self.offsets[:-1]):
-            g = "lora" if "lora_" in nm else ("aux_decoder" if nm.startswith("aux_decoder") else "decode_head")
+            g = grad_group(nm)
             if g != cur:
                 cuts.append([g, a, a])
                 cur = g

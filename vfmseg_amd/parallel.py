@@ -55,10 +55,11 @@ def broadcast_params(model, src=0):
 def make_buckets(names, offsets, max_lora_buckets=2):
     """Contiguous [start, end) slices of the flat gradient buffer in production order.
     names/offsets as in FusedAdamW (offsets has len(names)+1 entries)."""
+    from .optim import grad_group
     groups = []
     cur = None
     for i, nm in enumerate(names):
-        g = "lora" if "lora_" in nm else ("aux_decoder" if nm.startswith("aux_decoder") else "decode_head")
+        g = grad_group(nm)
         if g != cur:
             groups.append([g, offsets[i], offsets[i + 1]])
             cur = g
@@ -135,6 +136,8 @@ class GradSync:
                 self.works = []
                 self.gflat.mul_(1.0 / self.world)
         self.done = [False] * len(self.buckets)
+        from . import backbones
+        backbones._PENDING_BACKWARD[0] = 0   # (a forward whose backward never ran must not hold the next step's "backbone_done" back)
 
     __call__ = finish
 
@@ -156,7 +159,8 @@ def bn_sync_fn(group=None):
 def attach(model, optim_wrapper, group=None):
     """Wire DP into a built model + OptimWrapper: parameter broadcast, gradient buckets, SyncBN exchange, and the
     backward-time bucket launches (heads' buckets when the backbone backward starts, the first LoRA bucket once the
-    blocks it covers are done; GradSync.finish() sends the rest and joins the side stream)."""
+    blocks it covers are done, the Rein bucket when the backbone backward ends; GradSync.finish() sends the rest and joins
+    the side stream)."""
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     if world == 1 and not (dist.is_available() and dist.is_initialized() and single_rank_rehearsal()):
         return None
@@ -166,7 +170,8 @@ def attach(model, optim_wrapper, group=None):
     gs = GradSync(opt.gflat, buckets, group)
     optim_wrapper.grad_sync = gs
     from . import backbones
-    head_ids = [i for i, b in enumerate(buckets) if not b[0].startswith("lora")]
+    head_ids = [i for i, b in enumerate(buckets) if not b[0].startswith("lora") and b[0] != "reins"]
+    rein_ids = [i for i, b in enumerate(buckets) if b[0] == "reins"]   # shared by all layers: final when the backbone backward ends
     lora_ids = [i for i, b in enumerate(buckets) if b[0].startswith("lora")]
     # block index whose completion finalises LoRA bucket k: the smallest block number among the parameters it holds
     last_block = {}
@@ -183,7 +188,12 @@ def attach(model, optim_wrapper, group=None):
         if li in last_block:
             gs.ready(last_block[li])
 
+    def backbone_done():
+        for i in rein_ids:
+            gs.ready(i)
+
     backbones.BACKWARD_EVENTS["heads_done"], backbones.BACKWARD_EVENTS["block_done"] = heads_done, block_done
+    backbones.BACKWARD_EVENTS["backbone_done"] = backbone_done if rein_ids else None
     head = getattr(model, "decode_head", None)
     if head is not None and hasattr(head, "bn_sync"):
         head.bn_sync, head.bn_world = bn_sync_fn(group), world

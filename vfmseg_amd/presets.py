@@ -4,6 +4,7 @@ Values (not code) taken from the reference config tree:
   configs/_base_/models/lora_dinov2_ms_masked.py:1-87   -> dinov2_ms_masked()
   configs/_base_/models/lora_dinov2_linear.py:1-53      -> dinov2_linear()
   configs/dg/gta2citys/dg_lora_dinov2_ms_masked.py:10-29 -> optim_cfg()
+  configs/_base_/models/rein_dinov2_linear.py:1-61      -> rein_dinov2_linear()
 They use the reference's registry `type=` names and ctor kwargs so a user's own
 configs/dg/*.py dicts are interchangeable with these.
 """
@@ -121,6 +122,29 @@ def dinov2_linear(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
         decode_head=linear_head(embed_dim),
         train_cfg=dict(),
         test_cfg=dict(mode="whole"),
+    )
+
+
+def reins_cfg(depth=24, embed_dim=1024, token_length=100, lora_dim=16):
+    """configs/_base_/models/rein_dinov2_linear.py:17-25"""
+    return dict(type="LoRAReins", token_length=token_length, embed_dims=embed_dim, num_layers=depth, patch_size=16,
+                link_token_to_query=False, lora_dim=lora_dim)
+
+
+def rein_dinov2_linear(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
+    """configs/_base_/models/rein_dinov2_linear.py: EncoderDecoder, frozen DINOv2-L with the Rein adapter after every block, LinearHead,
+    slide test.  `checkpoint` (the converted DINOv2 weights, bare keys) goes where the reference puts it: the backbone's init_cfg, which
+    ReinsDinoVisionTransformer reads at construction."""
+    bb = dict(type="ReinsDinoVisionTransformer", reins_config=reins_cfg(depth, embed_dim), **{k: v for k, v in
+              dinov2_backbone(depth, embed_dim, num_heads).items() if k != "type"})
+    bb["init_cfg"] = dict(type="Pretrained", checkpoint=checkpoint)
+    return dict(
+        type="EncoderDecoder",
+        data_preprocessor=dict(_PREPROC, size=(512, 512)),
+        backbone=bb,
+        decode_head=linear_head(embed_dim),
+        train_cfg=dict(),
+        test_cfg=dict(mode="slide", stride=[320, 320], crop_size=[512, 512]),
     )
 
 

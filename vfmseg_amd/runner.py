@@ -53,6 +53,18 @@ def find_latest_checkpoint(work_dir):
     return best[1] if best else None
 
 
+def _pack_np_state(st):
+    """np.random.get_state() as plain tensors / numbers, so that a checkpoint stays loadable with torch.load's weights-only default."""
+    name, keys, pos, has_gauss, cached = st
+    return dict(name=str(name), keys=torch.from_numpy(np.asarray(keys).astype(np.int64)), pos=int(pos), has_gauss=int(has_gauss), cached=float(cached))
+
+
+def _unpack_np_state(st):
+    if isinstance(st, dict):
+        return (st["name"], st["keys"].numpy().astype(np.uint32), st["pos"], st["has_gauss"], st["cached"])
+    return st   # (checkpoints written before the packed form hold numpy's own tuple)
+
+
 class Runner:
     def __init__(self, cfg, model, optim_wrapper, loader, work_dir, rank=0, world=1):
         self.cfg, self.model, self.ow, self.loader, self.work_dir = cfg, model, optim_wrapper, loader, work_dir
@@ -72,7 +84,14 @@ class Runner:
         torch.manual_seed(seed)
         model = MODELS.build(cfg["model"])
         if cfg.get("synthetic_init", True):
-            model.load_state_dict(synth_like(model.state_dict()))
+            sd = synth_like(model.state_dict())
+            # (a Rein backbone's state_dict() leaves its frozen base out: those weights get their synthetic values by parameter name)
+            hidden = {k: p.detach() for k, p in model.named_parameters() if k not in sd}
+            if getattr(getattr(model, "backbone", None), "pretrained", None) is not None:
+                model.load_state_dict(sd, strict=False)    # that base was loaded from its checkpoint (init_cfg): it stays
+            else:
+                sd.update(synth_like(hidden))
+                model.load_state_dict(sd)
         model = model.cuda().train()
         ow_cfg = dict(cfg.get("optim_wrapper", {}))
         ctor = OPTIM_WRAPPER_CONSTRUCTORS.get(ow_cfg.get("constructor", "PEFTOptimWrapperConstructor")) or PEFTOptimWrapperConstructor
@@ -110,7 +129,7 @@ class Runner:
 
     def _rng_state(self):
         from . import functional as Fh
-        return dict(iter=self.iter, loader_pos=getattr(self.loader, "i", None), np_random=np.random.get_state(),
+        return dict(iter=self.iter, loader_pos=getattr(self.loader, "i", None), np_random=_pack_np_state(np.random.get_state()),
                     mask_rng=dict(Fh._seed_state), torch_rng=torch.get_rng_state())
 
     def save_rank_state(self, path):
@@ -156,7 +175,7 @@ class Runner:
             elif hasattr(self.loader, "i"):
                 self.loader.i = meta["loader_pos"]
         if meta.get("np_random") is not None:
-            np.random.set_state(meta["np_random"])
+            np.random.set_state(_unpack_np_state(meta["np_random"]))
         if meta.get("mask_rng") is not None:
             Fh._seed_state.update(meta["mask_rng"])
         if meta.get("torch_rng") is not None:

@@ -165,6 +165,8 @@ class EncoderDecoder(nn.Module):
         if hasattr(bb, "forward_tokens"):
             if bb.__class__.__name__ == "LoRABackbone":
                 xcat, (hp, wp) = bb.forward_tokens(jobs)
+            elif hasattr(bb, "adapter_training"):   # a ViT that carries its own adapters (Rein) says whether they are being trained
+                xcat, (hp, wp) = bb.forward_tokens(jobs, training=bb.adapter_training())
             else:
                 xcat, (hp, wp) = bb.forward_tokens(jobs, training=False)
             return xcat, hp, wp
