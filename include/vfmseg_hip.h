@@ -343,6 +343,22 @@ int vfm_upsample_ce(const float* logits_low, const int64_t* label, int B, int h,
 /* After vfm_upsample_ce: loss[0] = scale * sum(loss_parts[0..n)), acc[0] = 100 * counts[0] / (counts[1] + eps) (mmseg `accuracy`
  * over the valid pixels, linear_head.py:95-108), then counts is reset to (0, 0) for the next call. */
 int vfm_ce_finish(const float* loss_parts, long n, float scale, int32_t* counts, float eps, float* loss, float* acc, void* stream);
+/* ---- HRDA multi-resolution fusion (rein/models/heads/hrda.py:149-191), fp32 NHWC in both builds of the library ----
+ *   lr [B,h,w,C] LinearHead logits of the half-size image; a [B,ha,wa,C] AttentionHead logits at feature resolution (any ha <= h);
+ *   hr [B,hc,wc,C] high-resolution logits sitting at (Y0,X0) of the [2h,2w] output grid (training: the crop; inference: the whole grid).
+ *   att = mask * bilinear(sigmoid(a) -> h x w), mask = 1 on rows [my0,my1) x columns [mx0,mx1) of the lr grid (no crop: 0,h,0,w);
+ *   fused [B,2h,2w,C] = up2(att) * hr_inserted + up2((1 - att) * lr), up2 = bilinear x2; align_corners=False, clamped edges throughout.
+ * vfm_hrda_fuse_fwd: one launch over the output elements; optional att_out / lr_scaled_out [B,h,w,C] (att for the backward, (1 - att) * lr
+ *   = the reference's second return value), NULL to skip.
+ * vfm_hrda_fuse_bwd: from d_fused and the saved att: d_hr = up2(att) * d_fused on the crop, d_lr = (1 - att) * up2^T(d_fused),
+ *   d_a = resize^T(mask * (up2^T(d_fused * hr_inserted) - lr * up2^T(d_fused))) * s (1 - s).  The adjoint resizes are gathers in a fixed
+ *   order (no floating-point atomics: bit-reproducible); every element of d_lr, d_a, d_hr is written.  d_att_ws: scratch [B,h,w,C]. */
+int vfm_hrda_fuse_fwd(const float* lr, const float* a, const float* hr, int B, int h, int w, int C, int ha, int wa, int hc, int wc,
+                      int Y0, int X0, int my0, int my1, int mx0, int mx1, float* fused, float* att_out, float* lr_scaled_out,
+                      void* stream);
+int vfm_hrda_fuse_bwd(const float* d_fused, const float* lr, const float* a, const float* hr, const float* att, int B, int h, int w,
+                      int C, int ha, int wa, int hc, int wc, int Y0, int X0, int my0, int my1, int mx0, int mx1, float* d_lr,
+                      float* d_a, float* d_hr, float* d_att_ws, void* stream);
 /* deterministic sum of n floats -> out[0] (out[0] *= scale) */
 int vfm_reduce_sum(const float* x, long n, float scale, float* out, void* stream);
 

@@ -692,3 +692,55 @@ class UpsampleCEFn(torch.autograd.Function):
         if ctx.lw != 1.0:
             ops.axpby(g, ctx.lw, g, 0.0)
         return g, None, None, None
+
+
+class UpsampleCEAllFn(torch.autograd.Function):
+    """UpsampleCEFn with the accuracy of rein/models/heads/utils.py:35-80 (the HRDA head's): 100 * correct / label.numel() - ignored
+    pixels stay in the denominator and count as wrong.  Same fused kernel; the raw (hits, valid) counters are finished here."""
+
+    @staticmethod
+    def forward(ctx, logits_low, label, ignore_index, loss_weight):
+        loss, counts, dl = ops.upsample_ce(logits_low.contiguous(), label, ignore_index, need_grad=True)
+        ctx.save_for_backward(dl)
+        ctx.lw = loss_weight
+        acc = counts[:1].to(torch.float32)
+        ops.axpby(acc, 100.0 / label.numel(), acc, 0.0)
+        ctx.mark_non_differentiable(acc)
+        if loss_weight != 1.0:
+            ops.axpby(loss, loss_weight, loss, 0.0)
+        return loss.view(()), acc
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (g,) = ctx.saved_tensors
+        ops.scale_by_device_scalar(g, dloss.contiguous().view(1))
+        if ctx.lw != 1.0:
+            ops.axpby(g, ctx.lw, g, 0.0)
+        return g, None, None, None
+
+
+class HrdaFuseFn(torch.autograd.Function):
+    """(fused [B,2h,2w,C], (1 - att) * lr [B,h,w,C]) = HRDA fusion of lr [B,h,w,C], a [B,ha,wa,C], hr [B,hc,wc,C] (hrda.py:149-191; ops.hrda_fuse_fwd).
+    offset = (Y0, X0) of hr in the output grid, mask_box = (y0, y1, x0, x1) on the lr grid or None.  The second output carries no gradient
+    (the reference's lr loss, lr_loss_weight > 0, is not on this path)."""
+
+    @staticmethod
+    def forward(ctx, lr, a, hr, offset, mask_box):
+        lr, a, hr = lr.contiguous(), a.contiguous(), hr.contiguous()
+        B, h, w, C = lr.shape
+        fused = torch.empty(B, 2 * h, 2 * w, C, dtype=torch.float32, device=lr.device)
+        att = torch.empty_like(lr)
+        lrs = torch.empty_like(lr)
+        ops.hrda_fuse_fwd(lr, a, hr, offset, mask_box, fused, att, lrs)
+        ctx.save_for_backward(lr, a, hr, att)
+        ctx.geo = (tuple(offset), None if mask_box is None else tuple(mask_box))
+        ctx.mark_non_differentiable(lrs)
+        return fused, lrs
+
+    @staticmethod
+    def backward(ctx, d_fused, _):
+        lr, a, hr, att = ctx.saved_tensors
+        offset, mask_box = ctx.geo
+        d_lr, d_a, d_hr = torch.empty_like(lr), torch.empty_like(a), torch.empty_like(hr)
+        ops.hrda_fuse_bwd(d_fused.contiguous(), lr, a, hr, att, offset, mask_box, d_lr, d_a, d_hr)
+        return d_lr, d_a, d_hr, None, None

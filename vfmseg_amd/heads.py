@@ -400,3 +400,185 @@ class VFMHead(BaseDecodeHead):
     def loss(self, inputs, seg_logits_embed, seg_label, query=None, return_logits=False):
         lg = self.forward_tokens(as_featpack(inputs, self.in_index), seg_logits_embed)
         return self._loss_from_lowres(lg, seg_label, return_logits)
+
+
+# ------------------------------------------------------------------------------------------------ HRDA
+@MODELS.register_module()
+class AttentionHead(BaseDecodeHead):
+    """rein/models/heads/attention_head.py:10-37: the scale-attention logits of HRDA - 1x1 fusion conv (no bias) + GN + ReLU over the
+    four concatenated taps, Dropout2d, conv_seg.  Output at feature resolution, [B, hp, wp, classes] fp32."""
+
+    def __init__(self, interpolate_mode="bilinear", **kwargs):
+        super().__init__(input_transform="multiple_select", **kwargs)
+        n = len(self.in_channels)
+        assert n == len(self.in_index) == 4
+        if (self.norm_cfg or {}).get("type") != "GN":
+            raise NotImplementedError("AttentionHead: only norm_cfg=dict(type='GN') (the reference config) is on the HIP path")
+        cin, ch, groups = self.in_channels[0] * n, self.channels, self.norm_cfg.get("num_groups", 32)
+
+        class _ConvModule(nn.Module):  # mmcv ConvModule(norm=GN): conv (no bias) -> gn -> ReLU
+            def __init__(s):
+                super().__init__()
+                s.conv = nn.Conv2d(cin, ch, 1, bias=False)
+                s.gn = nn.GroupNorm(groups, ch)
+
+        self.fusion_conv = _ConvModule()
+
+    @_fp32_on_fp32_taps
+    def forward_tokens(self, fp):
+        cd = compute_dtype()
+        B, P = fp.B, fp.hp * fp.wp
+        fc = self.fusion_conv
+        y = Fh.linear(fp.xcat, fc.conv.weight, "conv1x1", out_dtype=torch.float32)
+        y = Fh.group_norm_act(y, fc.gn.weight, fc.gn.bias, B, P, fc.gn.num_groups, fc.gn.eps, ops.ACT_RELU, cd)
+        y = Fh.dropout(y, self.dropout_ratio, self.training, rows_per_group=P)  # Dropout2d: per (image, channel)
+        lg = Fh.linear(y, self.conv_seg.weight, "conv1x1", bias=self.conv_seg.bias, out_dtype=torch.float32)
+        return lg.view(B, fp.hp, fp.wp, -1)
+
+    def forward(self, inputs):
+        return self.forward_tokens(as_featpack(inputs, self.in_index)).permute(0, 3, 1, 2)
+
+
+def scale_box(box, scale):
+    """hrda.py:26-36: truncation, not floor division of the floats' quotient."""
+    y1, y2, x1, x2 = box
+    return int(y1 / scale), int(y2 / scale), int(x1 / scale), int(x2 / scale)
+
+
+@MODELS.register_module()
+class HRDAHead(BaseDecodeHead):
+    """rein/models/heads/hrda.py:39-306 with a LinearHead as `head` and an AttentionHead as `scale_attention`: LR logits of the half-size
+    image and HR logits of a crop (training) or of overlapping crops (prediction), fused by the learned scale attention in one kernel
+    (functional.HrdaFuseFn).  Its own `conv_seg` is never used (hrda.py:72-76 keeps it; so do checkpoints): it is frozen here, since a
+    parameter without a gradient is skipped by torch's AdamW but would be decayed by the fused one."""
+
+    def __init__(self, seg_head, single_scale_head, lr_loss_weight=0, hr_loss_weight=0, scales=[1], enable_hr_crop=False,
+                 hr_slide_inference=True, **kwargs):
+        if not isinstance(single_scale_head, dict):
+            raise NotImplementedError(f"HRDAHead: single_scale_head={single_scale_head!r} names a head the reference cannot build either (hrda.py:80)")
+        if seg_head.get("type") != "LinearHead" or single_scale_head.get("type") != "AttentionHead":
+            raise NotImplementedError("HRDAHead: only seg_head=LinearHead with single_scale_head=AttentionHead (DAFormer / ASPP heads are not on the HIP path)")
+        if lr_loss_weight > 0:
+            raise NotImplementedError("HRDAHead: lr_loss_weight > 0 is not used by the reference config and not implemented")
+        super().__init__(in_channels=seg_head["in_channels"][0], channels=seg_head["channels"], num_classes=seg_head["num_classes"])
+        self.os = 4
+        self.head = MODELS.build(seg_head)
+        self.scale_attention = MODELS.build(single_scale_head)
+        for p in self.conv_seg.parameters():
+            p.requires_grad = False
+        self.lr_loss_weight, self.hr_loss_weight = lr_loss_weight, hr_loss_weight
+        self.scales = scales
+        self.enable_hr_crop = enable_hr_crop
+        self.hr_crop_box = None
+        self.hr_slide_inference = hr_slide_inference
+        self.debug = False
+
+    def train(self, mode=True):
+        super().train(mode)
+        for p in self.conv_seg.parameters():
+            p.requires_grad = False
+        return self
+
+    def set_hr_crop_box(self, boxes):
+        self.hr_crop_box = boxes
+
+    def reset_crop(self):
+        self.hr_crop_box = None
+
+    def hr_crop_slice(self, scale):
+        y1, y2, x1, x2 = scale_box(self.hr_crop_box, scale)
+        return slice(y1, y2), slice(x1, x2)
+
+    def decode_hr(self, inp, bs):
+        """hrda.py:103-134.  {'features': FeatPack of crop-major images, 'boxes'}: the crops' logits summed into the os-4 grid and divided by
+        the cover count; a plain FeatPack: the head's logits.  NHWC fp32."""
+        if isinstance(inp, dict) and "boxes" in inp:
+            boxes = [scale_box(b, self.os) for b in inp["boxes"]]
+            lg = self.head.forward_tokens(inp["features"])
+            return self.merge_crops(lg, boxes, bs)
+        return self.head.forward_tokens(as_featpack(inp, self.head.in_index))
+
+    def merge_crops(self, lg, boxes, bs):
+        h_img, w_img = max(b[1] for b in boxes), max(b[3] for b in boxes)
+        C = lg.shape[-1]
+        wins = []
+        for i, (y1, y2, x1, x2) in enumerate(boxes):
+            assert (y2 - y1, x2 - x1) == tuple(lg.shape[1:3]), "crop logits and scaled box disagree"
+            wins.append((lg[i * bs:(i + 1) * bs], False, (y1, x1, y2 - y1, x2 - x1)))
+        preds = torch.empty(bs, C, h_img, w_img, dtype=torch.float32, device=lg.device)
+        if not ops.slide_gather(wins, preds):
+            preds.zero_()
+            count = torch.zeros(bs, 1, h_img, w_img, dtype=torch.float32, device=lg.device)
+            for t, nchw, box in wins:
+                ops.slide_accumulate(t, nchw, bs, t.shape[1], t.shape[2], C, preds, count, box)
+            ops.slide_finalize(preds, count)
+        out = torch.empty(bs, h_img, w_img, C, dtype=torch.float32, device=lg.device)
+        return ops.permute_copy(preds, (0, 2, 3, 1), out)
+
+    def fuse(self, lr_seg, att_logits, hr_seg):
+        """hrda.py:169-191 on NHWC maps: -> (fused [B,2h,2w,C], (1 - att) * lr)."""
+        B, h, w, C = lr_seg.shape
+        if self.hr_crop_box is not None:
+            y1, y2, x1, x2 = scale_box(self.hr_crop_box, self.os)
+            mask_box = scale_box(self.hr_crop_box, self.os / self.scales[0])
+            offset = (y1, x1)
+            assert (y2 - y1, x2 - x1) == tuple(hr_seg.shape[1:3]), "HR logits and the crop box / 4 disagree"
+        else:
+            mask_box, offset = None, (0, 0)
+            assert tuple(hr_seg.shape[1:3]) == (2 * h, 2 * w), "without a crop the HR logits cover the output grid"
+        return Fh.HrdaFuseFn.apply(lr_seg, att_logits, hr_seg, offset, mask_box)
+
+    def forward(self, inputs):
+        """inputs = [LR features, HR features]: FeatPacks (or tuples of NCHW taps); HR may be {'features', 'boxes'}.  NHWC fp32 logits
+        (fused, lr_seg, hr_seg).  In training the LinearHead runs twice - LR, then HR - as in the reference: its BatchNorm normalises each
+        call by that call's statistics and updates the running statistics twice."""
+        assert len(inputs) == 2
+        lr_inp, hr_inp = inputs
+        assert len(self.scales) == 2 and self.scales[1] / self.scales[0] == 2, "the fusion kernel up-samples by hr_scale / lr_scale = 2"
+        lr_fp = as_featpack(lr_inp, self.head.in_index)
+        lr_seg = self.head.forward_tokens(lr_fp)
+        hr_seg = self.decode_hr(hr_inp, lr_fp.B)
+        att = self.scale_attention.forward_tokens(lr_fp)
+        fused, lr_scaled = self.fuse(lr_seg, att, hr_seg)
+        return fused, lr_scaled, hr_seg
+
+    def forward_test(self, inputs):
+        return self.forward(inputs)[0]
+
+    def cal_losses(self, seg_logit, seg_label, weight):
+        """hrda.py:240-261: CE of the bilinearly up-sampled logits (the fused kernel pair) and rein/models/heads/utils.py:35-80's accuracy."""
+        loss, acc = Fh.UpsampleCEAllFn.apply(seg_logit, seg_label.squeeze(1).contiguous(), self.ignore_index,
+                                             self.loss_decode.loss_weight * weight)
+        return {"loss_seg": loss, "acc_seg": acc}
+
+    def losses(self, seg_logit, seg_label):
+        fused, _, hr_seg = seg_logit
+        if self.hr_loss_weight == 0:
+            return self.cal_losses(fused, seg_label, 1.0)
+        loss = self.cal_losses(fused, seg_label, 1.0 - self.lr_loss_weight - self.hr_loss_weight)
+        if self.enable_hr_crop:
+            y1, y2, x1, x2 = self.hr_crop_box
+            B, _, H, W = seg_label.shape
+            hr_label = torch.empty(B, y2 - y1, x2 - x1, dtype=torch.int64, device=seg_label.device)
+            ops.label_resize(seg_label.squeeze(1).contiguous(), hr_label, (H, W), (y1, x1, y2 - y1, x2 - x1))
+            hr_label = hr_label.unsqueeze(1)
+        else:
+            hr_label = seg_label
+        for k, v in self.cal_losses(hr_seg, hr_label, self.hr_loss_weight).items():
+            loss["hr." + k] = v
+        return loss
+
+    def forward_train(self, inputs, gt_semantic_seg):
+        if self.enable_hr_crop:
+            assert self.hr_crop_box is not None
+        losses = self.losses(self.forward(inputs), gt_semantic_seg)
+        self.reset_crop()
+        return losses
+
+    def loss(self, inputs, data_samples, train_cfg=None):
+        gt = torch.stack([d.gt_sem_seg.data for d in data_samples]).to(_device_of(inputs[0]))
+        return self.forward_train(inputs, gt)
+
+
+def _device_of(inp):
+    return inp.xcat.device if isinstance(inp, FeatPack) else inp[0].device

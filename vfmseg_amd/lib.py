@@ -158,6 +158,8 @@ SIGNATURES = {
     "vfm_label_resize": [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, vp],
     "vfm_unblock": [vp, vp, ci, ci, ci, ci, ci, ci, vp],
     "vfm_upsample_ce": [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp],
+    "vfm_hrda_fuse_fwd": [vp, vp, vp] + [ci] * 14 + [vp, vp, vp, vp],
+    "vfm_hrda_fuse_bwd": [vp, vp, vp, vp, vp] + [ci] * 14 + [vp, vp, vp, vp, vp],
     "vfm_reduce_sum": [vp, cl, cf, vp, vp],
     "vfm_ce_finish": [vp, cl, cf, vp, cf, vp, vp, vp],
     "vfm_conf_gate": [vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp],

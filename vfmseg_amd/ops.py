@@ -1053,6 +1053,47 @@ def upsample_ce_loss_acc(logits_low, label, ignore_index=255, need_grad=True):
     return out[0:1], out[1:2], dl
 
 
+def _hrda_geo(lr, a, hr, offset, mask_box):
+    B, h, w, Cc = lr.shape
+    _, ha, wa, _ = a.shape
+    _, hc, wc, _ = hr.shape
+    for t in (lr, a, hr):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == B and t.shape[3] == Cc, "fp32 NHWC maps of one batch"
+    Y0, X0 = offset
+    my0, my1, mx0, mx1 = mask_box if mask_box is not None else (0, h, 0, w)
+    return [int(v) for v in (B, h, w, Cc, ha, wa, hc, wc, Y0, X0, my0, my1, mx0, mx1)]
+
+
+def hrda_fuse_fwd(lr, a, hr, offset, mask_box, fused, att_out=None, lr_scaled_out=None):
+    """fused [B,2h,2w,C] = up2(att) * hr_inserted + up2((1 - att) * lr), att = mask * bilinear(sigmoid(a) -> h x w)  (hrda.py:149-191).
+    lr [B,h,w,C], a [B,ha,wa,C], hr [B,hc,wc,C] at `offset` = (Y0, X0) of the output grid; mask_box = (y0, y1, x0, x1) on the lr grid or
+    None (no crop).  Optional outputs att_out / lr_scaled_out [B,h,w,C]."""
+    lib = L.load()
+    geo = _hrda_geo(lr, a, hr, offset, mask_box)
+    B, h, w, Cc = geo[:4]
+    assert fused.dtype == torch.float32 and fused.is_contiguous() and tuple(fused.shape) == (B, 2 * h, 2 * w, Cc)
+    for t in (att_out, lr_scaled_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, h, w, Cc))
+    L.check(lib.vfm_hrda_fuse_fwd(L.ptr(lr), L.ptr(a), L.ptr(hr), *geo, L.ptr(fused), L.ptr(att_out), L.ptr(lr_scaled_out), L.stream()),
+            "vfm_hrda_fuse_fwd")
+    return fused
+
+
+def hrda_fuse_bwd(d_fused, lr, a, hr, att, offset, mask_box, d_lr, d_a, d_hr):
+    """Backward of hrda_fuse_fwd from d_fused and the saved att; writes every element of d_lr, d_a, d_hr (gathers, no float atomics)."""
+    lib = L.load()
+    geo = _hrda_geo(lr, a, hr, offset, mask_box)
+    B, h, w, Cc = geo[:4]
+    assert d_fused.dtype == torch.float32 and d_fused.is_contiguous() and tuple(d_fused.shape) == (B, 2 * h, 2 * w, Cc)
+    assert att.dtype == torch.float32 and att.is_contiguous() and att.shape == lr.shape
+    for t, s in ((d_lr, lr), (d_a, a), (d_hr, hr)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == s.shape
+    ws = workspace(lr.numel(), lr.device, "hrda_d_att")
+    L.check(lib.vfm_hrda_fuse_bwd(L.ptr(d_fused), L.ptr(lr), L.ptr(a), L.ptr(hr), L.ptr(att), *geo, L.ptr(d_lr), L.ptr(d_a), L.ptr(d_hr),
+                                  L.ptr(ws), L.stream()), "vfm_hrda_fuse_bwd")
+    return d_lr, d_a, d_hr
+
+
 def preprocess_u8(img_u8, out, mean, std, bgr_to_rgb, pad_val=0.0):
     """img_u8 uint8 [3,H,W] (cuda) -> out fp32 [3,Hp,Wp]: channel swap, normalise, pad (mmseg SegDataPreProcessor)."""
     lib = L.load()

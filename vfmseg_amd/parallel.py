@@ -195,6 +195,7 @@ def attach(model, optim_wrapper, group=None):
     backbones.BACKWARD_EVENTS["heads_done"], backbones.BACKWARD_EVENTS["block_done"] = heads_done, block_done
     backbones.BACKWARD_EVENTS["backbone_done"] = backbone_done if rein_ids else None
     head = getattr(model, "decode_head", None)
-    if head is not None and hasattr(head, "bn_sync"):
-        head.bn_sync, head.bn_world = bn_sync_fn(group), world
+    for m in (head.modules() if head is not None else []):   # the LinearHead itself, or the one inside an HRDAHead
+        if hasattr(m, "bn_sync"):
+            m.bn_sync, m.bn_world = bn_sync_fn(group), world
     return gs

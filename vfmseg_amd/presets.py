@@ -5,6 +5,7 @@ Values (not code) taken from the reference config tree:
   configs/_base_/models/lora_dinov2_linear.py:1-53      -> dinov2_linear()
   configs/dg/gta2citys/dg_lora_dinov2_ms_masked.py:10-29 -> optim_cfg()
   configs/_base_/models/rein_dinov2_linear.py:1-61      -> rein_dinov2_linear()
+  configs/_base_/models/lora_dinov2_hrda.py:1-78        -> dinov2_hrda()
 They use the reference's registry `type=` names and ctor kwargs so a user's own
 configs/dg/*.py dicts are interchangeable with these.
 """
@@ -145,6 +146,40 @@ def rein_dinov2_linear(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
         decode_head=linear_head(embed_dim),
         train_cfg=dict(),
         test_cfg=dict(mode="slide", stride=[320, 320], crop_size=[512, 512]),
+    )
+
+
+def attention_head(embed_dim=1024, channels=256, num_classes=19):
+    """configs/_base_/models/lora_dinov2_hrda.py:54-64 (no loss_decode: the head only feeds the scale attention)"""
+    return dict(
+        type="AttentionHead",
+        in_channels=[embed_dim] * 4,
+        in_index=[0, 1, 2, 3],
+        channels=channels,
+        dropout_ratio=0.1,
+        num_classes=num_classes,
+        norm_cfg=dict(type="GN", num_groups=32),
+        align_corners=False,
+    )
+
+
+def dinov2_hrda(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
+    """configs/_base_/models/lora_dinov2_hrda.py: the HRDA multi-resolution baseline - LoRA DINOv2-L, HRDAHead (LinearHead + AttentionHead),
+    1024^2 training images with a 512^2 half-size pass and a 512^2 full-resolution crop, 1024 / 682 sliding test."""
+    return dict(
+        type="HRDAEncoderDecoder",
+        data_preprocessor=dict(_PREPROC, size=(1024, 1024)),
+        backbone=dict(type="LoRABackbone", backbone=dinov2_backbone(depth, embed_dim, num_heads), checkpoint=checkpoint,
+                      Lora_config=lora_cfg()),
+        decode_head=dict(type="HRDAHead", seg_head=linear_head(embed_dim), single_scale_head=attention_head(embed_dim),
+                         hr_loss_weight=0.1),
+        scales=[1, 0.5],
+        hr_crop_size=(512, 512),
+        feature_scale=0.5,
+        crop_coord_divisible=8,
+        hr_slide_inference=True,
+        train_cfg=dict(),
+        test_cfg=dict(mode="slide", stride=[682, 682], crop_size=[1024, 1024]),
     )
 
 

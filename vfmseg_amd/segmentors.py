@@ -601,3 +601,137 @@ class MsVFMEncoderDecoder(EncoderDecoder):
             if had_mask is not None:
                 dec.mask_enable = had_mask
         return preds
+
+
+@MODELS.register_module()
+class HRDAEncoderDecoder(EncoderDecoder):
+    """rein/models/segmentors/hrda_encoder_decoder.py:62-447 (the HRDA multi-resolution baseline): the half-size image and a random
+    full-resolution crop (training) or overlapping full-resolution crops (prediction) go through ONE backbone call; the HRDAHead fuses
+    their logits by a learned scale attention."""
+
+    def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None, pretrained=None,
+                 init_cfg=None, scales=[1], hr_crop_size=None, hr_slide_inference=True, hr_slide_overlapping=True,
+                 crop_coord_divisible=1, blur_hr_crop=False, feature_scale=1, data_preprocessor=None):
+        if blur_hr_crop:
+            raise NotImplementedError("HRDAEncoderDecoder: blur_hr_crop is not used by the reference config and not implemented")
+        if (test_cfg or {}).get("test_time_aug", False) or (test_cfg or {}).get("flip", False):
+            raise NotImplementedError("HRDAEncoderDecoder: test_time_aug / flip inside slide_inference are not implemented (use tools/test.py --tta)")
+        scales = sorted(scales)
+        decode_head = dict(decode_head)
+        decode_head["scales"] = scales
+        decode_head["enable_hr_crop"] = hr_crop_size is not None
+        decode_head["hr_slide_inference"] = hr_slide_inference
+        super().__init__(backbone=backbone, decode_head=decode_head, neck=neck, auxiliary_head=auxiliary_head, train_cfg=train_cfg,
+                         test_cfg=test_cfg, data_preprocessor=data_preprocessor)
+        assert len(scales) == 2 and scales[1] == 1, "HRDA runs on two scales, the larger one the image itself"
+        self.local_iter = 0
+        self.scales = scales
+        self.feature_scale = feature_scale
+        self.crop_size = hr_crop_size
+        self.hr_slide_inference = hr_slide_inference
+        self.hr_slide_overlapping = hr_slide_overlapping
+        self.crop_coord_divisible = crop_coord_divisible
+        self.orginal_slide_inference = self.test_cfg.get("orginal_slide_inference", False)
+        self.fixed_crop_box = None      # tests pin the RNG consumer
+        self.last_crop_box = None
+        self.sequential_windows = False  # one backbone call per outer slide window instead of one for all of them (same sums)
+
+    # ---- features
+    def _hr_tokens(self, jobs):
+        return self._tokens(jobs)
+
+    def _lr_image(self, img):
+        B, _, H, W = img.shape
+        s = self.scales[0]
+        lh, lw = int(H * s), int(W * s)
+        lr_img = torch.empty(B, 3, lh, lw, dtype=torch.float32, device=img.device)
+        return ops.resize_bilinear(img, True, B, H, W, 3, lr_img, 1, (lh, lw), scale_factor=s)   # F.interpolate(scale_factor=s): source scale 1/s
+
+    # ---- training (:305-392)
+    def loss(self, inputs, data_samples):
+        return self.forward_train(inputs, data_samples)
+
+    def forward_train(self, img, data_samples):
+        B, _, H, W = img.shape
+        assert self.crop_size is not None, "training needs hr_crop_size"
+        lr_img = self._lr_image(img)
+        box = self.fixed_crop_box or get_crop_bbox(H, W, self.crop_size, self.crop_coord_divisible)
+        self.last_crop_box = box
+        y1, y2, x1, x2 = box
+        assert tuple(lr_img.shape[2:]) == (y2 - y1, x2 - x1), "LR pass and HR crop must share the token grid to be batched"
+        xcat, hp, wp = self._hr_tokens([(lr_img, None), (img, box)])
+        P = hp * wp
+        feats = [FeatPack(xcat[:B * P], B, hp, wp), FeatPack(xcat[B * P:], B, hp, wp)]
+        self.decode_head.set_hr_crop_box(box)
+        try:
+            losses = add_prefix(self.decode_head.loss(feats, data_samples, self.train_cfg), "decode")
+        finally:
+            self.decode_head.reset_crop()
+        self.local_iter += 1
+        return losses
+
+    # ---- prediction (:125-150, 275-303)
+    def _crop_boxes(self, H, W):
+        stride = [e // 2 for e in self.crop_size] if self.hr_slide_overlapping else list(self.crop_size)
+        return grid_boxes(H, W, self.crop_size, stride)
+
+    def fused_lowres(self, img):
+        """The head's fused logits of whole images, NHWC [B, H/4, W/4, classes]: LR pass on the half-size image, HR pass over the
+        `hr_crop_size` crops (stride crop / 2 when overlapping), everything that shares a token grid in one backbone call."""
+        B, _, H, W = img.shape
+        self.decode_head.reset_crop()
+        if self.orginal_slide_inference:
+            return self.decode_head.head.forward_tokens(self.extract_feat(img))
+        lr_img = self._lr_image(img)
+        if not self.hr_slide_inference:
+            lr_x, hp, wp = self._hr_tokens([(lr_img, None)])
+            hr_x, hph, wph = self._hr_tokens([(img, None)])
+            return self.decode_head.forward_test([FeatPack(lr_x, B, hp, wp), FeatPack(hr_x, B, hph, wph)])
+        boxes = self._crop_boxes(H, W)
+        if tuple(lr_img.shape[2:]) == tuple(self.crop_size):
+            xcat, hp, wp = self._hr_tokens([(lr_img, None)] + [(img, b) for b in boxes])
+            P = hp * wp
+            lr_fp, hr_fp = FeatPack(xcat[:B * P], B, hp, wp), FeatPack(xcat[B * P:], B * len(boxes), hp, wp)
+        else:
+            lr_x, hp, wp = self._hr_tokens([(lr_img, None)])
+            hr_x, hph, wph = self._hr_tokens([(img, b) for b in boxes])
+            lr_fp, hr_fp = FeatPack(lr_x, B, hp, wp), FeatPack(hr_x, B * len(boxes), hph, wph)
+        return self.decode_head.forward_test([lr_fp, dict(features=hr_fp, boxes=[list(b) for b in boxes])])
+
+    def encode_decode(self, inputs, batch_img_metas, upscale_pred=True):
+        lg = self.fused_lowres(inputs)
+        if not upscale_pred:
+            return lg.permute(0, 3, 1, 2)
+        B, h, w, C = lg.shape
+        out = torch.empty(B, C, inputs.shape[2], inputs.shape[3], dtype=torch.float32, device=inputs.device)
+        return ops.resize_bilinear(lg, False, B, h, w, C, out, 1, tuple(inputs.shape[2:]))
+
+    def slide_inference(self, inputs, batch_img_metas):
+        """mmseg's slide merge over `test_cfg.crop_size` windows (batched_slide=True and the per-window loop have the same arithmetic):
+        the windows are a batch - one backbone call for the LR images and HR crops of all of them - unless `sequential_windows`."""
+        B, _, H, W = inputs.shape
+        boxes = grid_boxes(H, W, self.test_cfg.crop_size, self.test_cfg.stride)
+        if self.sequential_windows:
+            lgs = [self.fused_lowres(self._window_batch(inputs, [b])) for b in boxes]
+        else:
+            lg = self.fused_lowres(self._window_batch(inputs, boxes))
+            lgs = [lg[j * B:(j + 1) * B] for j in range(len(boxes))]
+        wins = [(lgs[j], False, (y1, x1, y2 - y1, x2 - x1)) for j, (y1, y2, x1, x2) in enumerate(boxes)]
+        return self._merge_windows(wins, B, self.out_channels, H, W, inputs.device)
+
+
+@MODELS.register_module()
+class FrozenHRDAEncoderDecoder(HRDAEncoderDecoder):
+    """hrda_encoder_decoder.py:450-464: the backbone stays in eval mode, runs without a graph and none of its parameters train."""
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.backbone.eval()
+        for p in self.backbone.parameters():
+            p.requires_grad = False
+        return self
+
+    def _hr_tokens(self, jobs):
+        with torch.no_grad():
+            xcat, hp, wp = self._tokens(jobs)
+        return xcat.detach(), hp, wp
