@@ -1,0 +1,12 @@
+# Frozen DINOv2-L + SegformerHead (only the head trains), sliding-window test (512 / 341)
+# (reference: configs/dg/gta2citys/dg_fzn_dinov2_Segformer_512x512_bs1x4.py -> configs/_base_/models/dinov2_SegFormer_frozen.py).
+from vfmseg_amd import presets
+
+crop_size = (512, 512)
+num_classes = 19
+model = presets.frozen_dinov2_segformer()
+_o = presets.optim_cfg()
+optim_wrapper = _o["optim_wrapper"]
+param_scheduler = _o["param_scheduler"]
+randomness = dict(seed=0)
+env_cfg = dict(dist_cfg=dict(backend="nccl"))

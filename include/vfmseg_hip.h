@@ -150,6 +150,15 @@ int vfm_groupnorm_fwd(const float* x, const float* w, const float* b, float eps,
 /* ws for both: >= B*G*2 + B*64*2*C floats */
 int vfm_groupnorm_bwd(const void* dy, int dy_dt, const float* x, const float* w, const float* b, const float* stats,
                       int G, int act, float* dx, float* dw, float* db, float* ws, long B, long P, long C, void* stream);
+/* The same GroupNorm (+ VFM_ACT_NONE / VFM_ACT_RELU) for maps of which one image's slab of 32 channels fits in a block's registers
+ * (mmseg SegformerHead: ConvModule GN on 32 x 32 tokens): forward in ONE launch, backward in two (dw / db accumulate; ws >= B*2*C floats).
+ * Fixed summation order, no atomics.  Coverage, as vfm_groupnorm_tile_ok(P, C, G) != 0 says: C % G == 0, C / G in {4, 8, 16, 32},
+ * C % 32 == 0, 0 < P <= 1024; both entries return VFM_E_SHAPE outside it. */
+int vfm_groupnorm_tile_ok(long P, long C, int G);
+int vfm_groupnorm_tile_fwd(const float* x, const float* w, const float* b, float eps, int G, int act, void* y, int y_dt,
+                           float* stats, long B, long P, long C, void* stream);
+int vfm_groupnorm_tile_bwd(const void* dy, int dy_dt, const float* x, const float* w, const float* b, const float* stats,
+                           int G, int act, float* dx, float* dw, float* db, float* ws, long B, long P, long C, void* stream);
 /* BatchNorm (nn.SyncBatchNorm, linear_head.py:44) on [rows, C]: partial moments -> (sum, sumsq) fp32 [2,C] */
 int vfm_bn_moments(const float* x, long rows, long C, float* sums, float* ws, void* stream);
 /* (sum, sumsq) over `count` rows (after the DP all-reduce of the sums, if any) -> mean_var fp32 [2,C] (biased var);

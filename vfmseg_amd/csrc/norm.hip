@@ -864,6 +864,187 @@ extern "C" int vfm_groupnorm_bwd(const void* dy, int dy_dt, const float* x, cons
   return VFM_OK;
 }
 
+// =============================================================================================== GroupNorm, one launch per map that fits on chip
+// SegformerHead's maps are 32 x 32 tokens per image: a slab of 32 channels (one 128-byte row piece, a whole number of groups) of ONE image
+// is 128 KB and sits in the registers of one 512-thread block - 8 lanes x float4 cover a row piece, the 8 waves cover 64 rows per step, 16
+// steps cover P <= 1024.  The block reads its tile once, takes the mean, then the centred second moment (two-pass: no cancellation), and
+// normalises out of registers.  Every sum has a fixed order: a xor butterfly over the lanes of a wave (all lanes end with the same bits),
+// then the 8 waves one after the other out of LDS.  No atomics.
+#define GNT_THREADS 512
+#define GNT_SLAB 32
+#define GNT_ROWS 64
+#define GNT_STEPS 16
+static inline bool gn_tile_covers(long P, long C, int G) {
+  if (G <= 0 || C <= 0 || P <= 0 || C % G) return false;
+  const long cg = C / G;   // a thread owns 4 adjacent channels: a group is 1, 2, 4 or 8 threads of a row piece
+  return (cg == 4 || cg == 8 || cg == 16 || cg == 32) && C % GNT_SLAB == 0 && P <= (long)GNT_ROWS * GNT_STEPS;
+}
+extern "C" int vfm_groupnorm_tile_ok(long P, long C, int G) { return gn_tile_covers(P, C, G) ? 1 : 0; }
+
+// sum of v over the threads that share a group: the rows of the wave (lane bits 3-5), the qpg quads of the group (low lane bits), the waves
+__device__ __forceinline__ float gnt_group_sum(float v, int qpg, float (*sh)[8]) {
+  v += __shfl_xor(v, 8, 64);
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  for (int o = 1; o < qpg; o <<= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63;
+  if (lane < 8) sh[threadIdx.x >> 6][lane] = v;
+  __syncthreads();
+  float r = 0.f;
+#pragma unroll
+  for (int k = 0; k < GNT_THREADS / 64; ++k) r += sh[k][lane & 7];
+  return r;
+}
+__device__ __forceinline__ void gnt_store4(float* p, float a, float b, float c, float d) { *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d); }
+__device__ __forceinline__ void gnt_store4(bf16_t* p, float a, float b, float c, float d) {
+  uint2 o;
+  o.x = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
+  o.y = (uint32_t)f32_to_bf16(c) | ((uint32_t)f32_to_bf16(d) << 16);
+  *reinterpret_cast<uint2*>(p) = o;
+}
+__device__ __forceinline__ float4 gnt_load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 gnt_load4(const bf16_t* p) {
+  const uint2 o = *reinterpret_cast<const uint2*>(p);
+  return make_float4(h16_lo(o.x), h16_hi(o.x), h16_lo(o.y), h16_hi(o.y));
+}
+
+template <typename TO>
+__global__ void __launch_bounds__(GNT_THREADS) k_gn_tile_fwd(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                             float eps, int G, int act, TO* __restrict__ y, float* __restrict__ stats, int P, int C) {
+  __shared__ float sh[2][GNT_THREADS / 64][8];
+  const int lane = threadIdx.x & 63, q = lane & 7, row0 = (threadIdx.x >> 6) * 8 + (lane >> 3);
+  const int c0 = blockIdx.x * GNT_SLAB + q * 4, cg = C / G, qpg = cg >> 2;
+  const long base = (long)blockIdx.y * P * C + c0;
+  float4 v[GNT_STEPS];
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) {
+    const int r = k * GNT_ROWS + row0;
+    v[k] = r < P ? gnt_load4(x + base + (long)r * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+  const float inv_n = 1.0f / ((float)P * (float)cg);
+  const float mean = gnt_group_sum(s, qpg, sh[0]) * inv_n;
+  float d = 0.f;
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) {
+    if (k * GNT_ROWS + row0 < P) {
+      const float a0 = v[k].x - mean, a1 = v[k].y - mean, a2 = v[k].z - mean, a3 = v[k].w - mean;
+      d += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+    }
+  }
+  const float rstd = 1.0f / sqrtf(gnt_group_sum(d, qpg, sh[1]) * inv_n + eps);
+  if (threadIdx.x < 8 && q % qpg == 0) {
+    const long i = (long)blockIdx.y * G + c0 / cg;
+    stats[i * 2] = mean;
+    stats[i * 2 + 1] = rstd;
+  }
+  const float4 wv = gnt_load4(w + c0), bv = gnt_load4(b + c0);
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) {
+    const int r = k * GNT_ROWS + row0;
+    if (r < P)
+      gnt_store4(y + base + (long)r * C, act_f((v[k].x - mean) * rstd * wv.x + bv.x, act), act_f((v[k].y - mean) * rstd * wv.y + bv.y, act),
+                 act_f((v[k].z - mean) * rstd * wv.z + bv.z, act), act_f((v[k].w - mean) * rstd * wv.w + bv.w, act));
+  }
+}
+/* GroupNorm + activation (NONE / RELU) in ONE launch where gn_tile_covers(); the contract of vfm_groupnorm_fwd otherwise */
+extern "C" int vfm_groupnorm_tile_fwd(const float* x, const float* w, const float* b, float eps, int G, int act, void* y, int y_dt,
+                                      float* stats, long B, long P, long C, void* stream) {
+  VFM_CHECK(gn_tile_covers(P, C, G) && B > 0 && B <= 65535, VFM_E_SHAPE, "vfm_groupnorm_tile_fwd: (P %ld, C %ld, G %d) is outside the tile kernel's coverage", P, C, G);
+  VFM_CHECK(act == VFM_ACT_NONE || act == VFM_ACT_RELU, VFM_E_UNSUPPORTED, "vfm_groupnorm_tile_fwd: activation");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(C / GNT_SLAB), (unsigned)B);
+  if (y_dt == VFM_BF16) hipLaunchKernelGGL(k_gn_tile_fwd<bf16_t>, grid, dim3(GNT_THREADS), 0, s, x, w, b, eps, G, act, (bf16_t*)y, stats, (int)P, (int)C);
+  else if (y_dt == VFM_F32) hipLaunchKernelGGL(k_gn_tile_fwd<float>, grid, dim3(GNT_THREADS), 0, s, x, w, b, eps, G, act, (float*)y, stats, (int)P, (int)C);
+  else VFM_FAIL(VFM_E_INVAL, "vfm_groupnorm_tile_fwd: dtype");
+  VFM_LAUNCH_CHECK();
+  return VFM_OK;
+}
+
+// backward: the block holds x and dy of its tile, forms dz = dy * act'(.) and xhat in place, reduces w * dz and w * dz * xhat per group and
+// dz, dz * xhat per channel (-> part[b][2][C], summed over the images by k_chan_fin_wb), and writes dx.
+template <typename TD>
+__global__ void __launch_bounds__(GNT_THREADS) k_gn_tile_bwd(const TD* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ b, const float* __restrict__ stats, int G, int act,
+                                                             float* __restrict__ dx, float* __restrict__ part, int P, int C) {
+  __shared__ float sh[2][GNT_THREADS / 64][8];
+  __shared__ float shc[GNT_THREADS / 64][2][GNT_SLAB];
+  const int lane = threadIdx.x & 63, q = lane & 7, wave = threadIdx.x >> 6, row0 = wave * 8 + (lane >> 3);
+  const int c0 = blockIdx.x * GNT_SLAB + q * 4, cg = C / G, qpg = cg >> 2;
+  const long base = (long)blockIdx.y * P * C + c0;
+  float4 v[GNT_STEPS], d[GNT_STEPS];
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) {
+    const int r = k * GNT_ROWS + row0;
+    v[k] = r < P ? gnt_load4(x + base + (long)r * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+    d[k] = r < P ? gnt_load4(dy + base + (long)r * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const long gi = (long)blockIdx.y * G + c0 / cg;
+  const float mean = stats[gi * 2], rstd = stats[gi * 2 + 1];
+  const float4 wv = gnt_load4(w + c0), bv = gnt_load4(b + c0);
+  float4 a1 = make_float4(0.f, 0.f, 0.f, 0.f), a2 = a1;   // per channel: sum dz, sum dz * xhat
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) {
+    if (k * GNT_ROWS + row0 < P) {
+#define GNT_ELEM(m)                                                   \
+  {                                                                   \
+    const float xh = (v[k].m - mean) * rstd;                          \
+    float dz = d[k].m;                                                \
+    if (act != VFM_ACT_NONE) dz *= act_grad_f(xh * wv.m + bv.m, act); \
+    v[k].m = xh, d[k].m = dz;                                         \
+    a1.m += dz, a2.m += dz * xh;                                      \
+  }
+      GNT_ELEM(x) GNT_ELEM(y) GNT_ELEM(z) GNT_ELEM(w)
+#undef GNT_ELEM
+    }
+  }
+  const float s1 = gnt_group_sum((wv.x * a1.x + wv.y * a1.y) + (wv.z * a1.z + wv.w * a1.w), qpg, sh[0]);
+  const float s2 = gnt_group_sum((wv.x * a2.x + wv.y * a2.y) + (wv.z * a2.z + wv.w * a2.w), qpg, sh[1]);
+  // channel sums over the rows: the lanes of a wave that hold the same quad, then the waves
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+    a1.x += __shfl_xor(a1.x, o, 64), a1.y += __shfl_xor(a1.y, o, 64), a1.z += __shfl_xor(a1.z, o, 64), a1.w += __shfl_xor(a1.w, o, 64);
+    a2.x += __shfl_xor(a2.x, o, 64), a2.y += __shfl_xor(a2.y, o, 64), a2.z += __shfl_xor(a2.z, o, 64), a2.w += __shfl_xor(a2.w, o, 64);
+  }
+  if (lane < 8) {
+    *reinterpret_cast<float4*>(&shc[wave][0][q * 4]) = a1;
+    *reinterpret_cast<float4*>(&shc[wave][1][q * 4]) = a2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * GNT_SLAB) {
+    const int kind = threadIdx.x >> 5, c = threadIdx.x & 31;
+    float r = 0.f;
+#pragma unroll
+    for (int k = 0; k < GNT_THREADS / 64; ++k) r += shc[k][kind][c];
+    part[((long)blockIdx.y * 2 + kind) * C + blockIdx.x * GNT_SLAB + c] = r;
+  }
+  const float inv_n = 1.0f / ((float)P * (float)cg);
+#pragma unroll
+  for (int k = 0; k < GNT_STEPS; ++k) {
+    const int r = k * GNT_ROWS + row0;
+    if (r < P)
+      gnt_store4(dx + base + (long)r * C, rstd * (d[k].x * wv.x - (s1 + v[k].x * s2) * inv_n), rstd * (d[k].y * wv.y - (s1 + v[k].y * s2) * inv_n),
+                 rstd * (d[k].z * wv.z - (s1 + v[k].z * s2) * inv_n), rstd * (d[k].w * wv.w - (s1 + v[k].w * s2) * inv_n));
+  }
+}
+/* two launches; dw / db ACCUMULATE when non-null; ws >= B*2*C floats */
+extern "C" int vfm_groupnorm_tile_bwd(const void* dy, int dy_dt, const float* x, const float* w, const float* b, const float* stats,
+                                      int G, int act, float* dx, float* dw, float* db, float* ws, long B, long P, long C, void* stream) {
+  VFM_CHECK(gn_tile_covers(P, C, G) && B > 0 && B <= 65535, VFM_E_SHAPE, "vfm_groupnorm_tile_bwd: (P %ld, C %ld, G %d) is outside the tile kernel's coverage", P, C, G);
+  VFM_CHECK(act == VFM_ACT_NONE || act == VFM_ACT_RELU, VFM_E_UNSUPPORTED, "vfm_groupnorm_tile_bwd: activation");
+  VFM_CHECK(ws, VFM_E_INVAL, "vfm_groupnorm_tile_bwd: ws");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(C / GNT_SLAB), (unsigned)B);
+  if (dy_dt == VFM_BF16) hipLaunchKernelGGL(k_gn_tile_bwd<bf16_t>, grid, dim3(GNT_THREADS), 0, s, (const bf16_t*)dy, x, w, b, stats, G, act, dx, ws, (int)P, (int)C);
+  else if (dy_dt == VFM_F32) hipLaunchKernelGGL(k_gn_tile_bwd<float>, grid, dim3(GNT_THREADS), 0, s, (const float*)dy, x, w, b, stats, G, act, dx, ws, (int)P, (int)C);
+  else VFM_FAIL(VFM_E_INVAL, "vfm_groupnorm_tile_bwd: dtype");
+  if (dw || db) hipLaunchKernelGGL(k_chan_fin_wb, dim3(cdiv(C, 64)), dim3(256), 0, s, ws, (int)B, (int)C, dw, db);
+  VFM_LAUNCH_CHECK();
+  return VFM_OK;
+}
+
 // =============================================================================================== BatchNorm
 __global__ void __launch_bounds__(256) k_bn_fin_sums(const float* __restrict__ ws, int slots, int C, float* __restrict__ sums) {
   // 64 channels x 4 slot groups per block, fixed combination order (the one-thread-per-channel walk over all slots was a chain of

@@ -4,6 +4,8 @@ Conventions: feature maps are token-major matrices [rows, C]; GEMM operands use 
 normalisation inputs / residual streams / losses are fp32.  Every Function returns gradients in the dtype of the
 corresponding forward input, so autograd never inserts a cast of its own.
 """
+import os
+
 import torch
 
 from .precision import is_half
@@ -452,6 +454,181 @@ class GroupNormActFn(torch.autograd.Function):
 
 def group_norm_act(x, w, b, B, P, groups=32, eps=1e-5, act=ops.ACT_NONE, out_dtype=None):
     return GroupNormActFn.apply(x, w, b, B, P, groups, eps, act, out_dtype or compute_dtype())
+
+
+# ---- SegformerHead's GroupNorms: the one-launch kernel where it covers the map, several norms' parameters side by side
+# Which form runs where the tile kernel covers the shape is decided by measurement (tools/segformer_time.py,
+# profiles/segformer_time.log): the one-launch forward is faster at every measured shape of the head; the two-launch backward is faster at
+# 64, 144 and 576 blocks (images x 32-channel slabs) and slower (19.9 vs 19.4 us) at the 16 blocks of the fusion norm of a 2-image batch,
+# which keeps the existing backward (both forms read and write the same `stats`).  64 is the smallest measured block count at which the
+# tile backward wins; nothing was measured between 16 and 64, so that range conservatively keeps the existing kernels.
+# VFMSEG_GN_TILE=1 / 0 forces the tile kernels (inside their coverage) / the three- and four-launch kernels of group_norm_act.
+GN_TILE_BWD_MIN_BLOCKS = 64
+GN_TILE_SLAB = 32      # channels per block of the tile kernels (GNT_SLAB in csrc/norm.hip; its coverage predicate asks C % 32 == 0)
+
+
+def gn_tile_selected(P, C, groups, B=None, backward=False):
+    v = os.environ.get("VFMSEG_GN_TILE", "")
+    if v == "0" or not ops.groupnorm_tile_ok(P, C, groups):
+        return False
+    if v == "1" or not backward:
+        return True
+    return B is None or B * (C // GN_TILE_SLAB) >= GN_TILE_BWD_MIN_BLOCKS
+
+
+class NormParamPack:
+    """fp32 [2, n*C] image (weights | biases) of n norms that run as ONE norm over n*C channels.  One batched copy launch re-packs it when
+    the parameters changed (optim.PARAM_EPOCH - the fused AdamW rewrites them behind torch's version counters - or a `_version`), not on
+    every call; the job table is rebuilt when a parameter moves (.cuda(), load into new storage).
+    The image is ONE buffer that a re-pack overwrites in place, and GroupNormCatFn saves views of it for its backward: that is sound
+    because parameters change only between a backward and the next forward (optimiser step, load_state_dict), never between a forward
+    and its own backward."""
+
+    def __init__(self):
+        self.key = self.buf = self.table = self.stamp = None
+        self.gkey = self.gbuf = self.gtable = None
+
+    def get(self, ws, bs):
+        key = tuple(p.data_ptr() for p in ws + bs)
+        if key != self.key:
+            C, n = ws[0].numel(), len(ws)
+            self.buf = torch.empty(2, n * C, dtype=torch.float32, device=ws[0].device)
+            jobs = [(p.detach().view(-1), self.buf[j][i * C:(i + 1) * C], (C,), (1,), (1,))
+                    for j, ps in enumerate((ws, bs)) for i, p in enumerate(ps)]
+            self.table, self.key, self.stamp = ops.CopyBatch(jobs), key, None
+        stamp = _PackCache._stamp(ws + bs)
+        if stamp != self.stamp:
+            self.table.run()
+            self.stamp = stamp
+        return self.buf[0], self.buf[1]
+
+    def grad_buffer(self, C, device):
+        """zeroed fp32 [2, C] the backward kernels accumulate dw | db into (one persistent buffer, one fill launch)"""
+        if self.gbuf is None or self.gbuf.shape[1] != C or self.gbuf.device != device:
+            self.gbuf, self.gkey = torch.empty(2, C, dtype=torch.float32, device=device), None
+        return self.gbuf.zero_()
+
+    def scatter(self, params, n):
+        """gbuf's 2 n slices into the parameters' gradients: ONE batched accumulate launch when every parameter has a slot in the
+        optimiser's flat gradient buffer (returns Nones), else the slices themselves (copies: gbuf is reused)."""
+        c = self.gbuf.shape[1] // n
+        parts = [self.gbuf[j, i * c:(i + 1) * c] for j in range(2) for i in range(n)]
+        tgts = [direct_grad_target(p) for p in params]
+        if any(t is None for t in tgts):
+            for part, t in zip(parts, tgts):
+                if t is not None:
+                    ops.axpby(part, 1.0, t.view(-1), 1.0)
+            return tuple(None if t is not None else part.clone() for part, t in zip(parts, tgts))
+        key = tuple(t.data_ptr() for t in tgts)
+        if key != self.gkey:
+            self.gtable = ops.CopyBatch([(part, t.view(-1), (c,), (1,), (1,), True) for part, t in zip(parts, tgts)])
+            self.gkey = key
+        self.gtable.run()
+        return (None,) * len(params)
+
+
+class GroupNormCatFn(torch.autograd.Function):
+    """GroupNorm + activation of n side-by-side norms of equal width as one norm over [rows, n*c] with n*groups groups (n = 1: a plain
+    GroupNorm).  The kernels are the tile pair where gn_tile_selected(), else those of GroupNormActFn."""
+
+    @staticmethod
+    def forward(ctx, x, B, P, groups, eps, act, out_dtype, pack, n, *wb):
+        x = x.contiguous()
+        C = x.shape[1]
+        ws, bs = wb[:n], wb[n:]
+        if n == 1:
+            w, b = ws[0].detach(), bs[0].detach()
+        else:
+            w, b = pack.get(ws, bs)
+        tile = gn_tile_selected(P, C, n * groups, B)
+        y = torch.empty(B * P, C, dtype=out_dtype, device=x.device)
+        stats = torch.empty(B, n * groups, 2, dtype=torch.float32, device=x.device)
+        (ops.groupnorm_tile_fwd if tile else ops.groupnorm_fwd)(x, w, b, eps, n * groups, act, y, stats, B, P)
+        ctx.save_for_backward(x, w, b, stats, *wb)
+        ctx.cfg = (B, P, n * groups, act, n, gn_tile_selected(P, C, n * groups, B, backward=True))
+        ctx.pack = pack
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b, stats, *wb = ctx.saved_tensors
+        B, P, G, act, n, tile = ctx.cfg
+        C = x.shape[1]
+        bwd = ops.groupnorm_tile_bwd if tile else ops.groupnorm_bwd
+        if n == 1:
+            dw, db, ret_w, ret_b = _norm_grad_slots(wb[0], wb[1], C, x.device)
+            dx = bwd(dy.contiguous(), x, w, b, stats, G, act, torch.empty_like(x), dw, db, B, P)
+            return (dx,) + (None,) * 8 + (ret_w, ret_b)
+        pack = ctx.pack
+        dwb = pack.grad_buffer(C, x.device)
+        dx = bwd(dy.contiguous(), x, w, b, stats, G, act, torch.empty_like(x), dwb[0], dwb[1], B, P)
+        return (dx,) + (None,) * 8 + pack.scatter(wb, n)
+
+
+def group_norm_cat_act(x, ws, bs, B, P, groups, eps, act, out_dtype=None, pack=None):
+    ws, bs = list(ws), list(bs)
+    return GroupNormCatFn.apply(x, B, P, groups, eps, act, out_dtype or compute_dtype(), pack, len(ws), *ws, *bs)
+
+
+class BranchLinearFn(torch.autograd.Function):
+    """n independent bias-free 1x1 convolutions on the n column blocks of one token-major matrix, as ONE batched GEMM each way:
+    y[:, i*N:(i+1)*N] = x[:, i*K:(i+1)*K] @ W_i^T  (x [M, n*K] compute dtype, y [M, n*N] fp32).  The batch runs through vfm_gemm's
+    `batch` / stride_a / stride_b / stride_c on column-offset views: no operand is copied."""
+
+    @staticmethod
+    def _views(x, n):
+        M, K = x.shape[0], x.shape[1] // n
+        return x.as_strided((n, M, K), (K, x.stride(0), 1), x.storage_offset())
+
+    @staticmethod
+    def forward(ctx, x, n, *weights):
+        cd = x.dtype
+        M, K = x.shape[0], x.shape[1] // n
+        N = weights[0].shape[0]
+        assert x.stride(1) == 1 and all(w.shape[0] == N and w[0].numel() == K for w in weights)
+        if is_half(cd) and (N % 64 or K % 64):
+            raise NotImplementedError(f"branch_linear: 16-bit operands need in / out channels in multiples of 64 (got {K} / {N})")
+        wp = PACKS.get(weights, ["conv1x1"] * n, [(N, K)] * n, K, K, cd)   # [n*N, K]
+        y = torch.empty(M, n * N, dtype=torch.float32, device=x.device)
+        ops.gemm(BranchLinearFn._views(x, n), wp.view(n, N, K), BranchLinearFn._views(y, n))
+        ctx.save_for_backward(x, wp, *weights)
+        ctx.n = n
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wp, *weights = ctx.saved_tensors
+        n, cd = ctx.n, x.dtype
+        M, K = x.shape[0], x.shape[1] // n
+        N = wp.shape[0] // n
+        dy = dy.contiguous()
+        g = dy if dy.dtype == cd else _cast_new(dy, cd)
+        g3, x3 = BranchLinearFn._views(g, n), BranchLinearFn._views(x, n)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(M, n * K, dtype=cd, device=x.device)
+            # dX_i = g_i @ W_i: the packed weight [N, K] is the [K', N'] operand (as in LinearFn.backward), all of its N rows valid in every
+            # batch (kb_rows = 0; a positive kb_rows would count the rows of ONE matrix sliced along K, vfm_gemm_desc)
+            ops.gemm(g3, wp.view(n, N, K), BranchLinearFn._views(dx, n), trans_b=True)
+        dws = [None] * n
+        if any(ctx.needs_input_grad[2:]):
+            gw = torch.empty(n, N, K, dtype=torch.float32, device=x.device)
+            if is_half(cd):
+                ops.gemm_tn_batched(g3, x3, gw, M)      # dW_i = g_i^T x_i, both operands token-major
+            else:
+                ops.gemm(g3, x3, gw, trans_a=True, trans_b=True)
+            for i, w_ in enumerate(weights):
+                if ctx.needs_input_grad[2 + i]:
+                    tgt = direct_grad_target(w_)
+                    if tgt is not None:
+                        ops.axpby(gw[i].view(-1), 1.0, tgt.view(-1), 1.0)
+                    else:
+                        dws[i] = gw[i].view(w_.shape)
+        return (dx, None) + tuple(dws)
+
+
+def branch_linear(x, weights):
+    return BranchLinearFn.apply(x, len(weights), *weights)
 
 
 class LayerNormFn(torch.autograd.Function):

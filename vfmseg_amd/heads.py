@@ -196,6 +196,75 @@ class LinearHead(BaseDecodeHead):
         return self.predict_by_feat(self.forward_tokens(as_featpack(inputs, self.in_index)), batch_img_metas)
 
 
+@MODELS.register_module()
+class SegformerHead(BaseDecodeHead):
+    """mmseg 1.2.2 SegformerHead (restated; mmseg is not a dependency): one ConvModule(in_channels[i], channels, 1) = bias-free 1x1 conv
+    + GN + ReLU per tap, each resized to tap 0's size (the identity here: all DINOv2 taps have one resolution), concatenated,
+    fusion_conv = ConvModule(channels * n, channels, 1), Dropout2d, conv_seg.  Logits at feature resolution, [B, hp, wp, classes] fp32.
+
+    On the HIP path the n embeddings are one batched GEMM over the column blocks of the feature pack and the n branch GroupNorms one
+    GroupNorm over [rows, n * channels] with n * num_groups groups (functional.BranchLinearFn / GroupNormCatFn): the concatenation is
+    never materialised."""
+
+    def __init__(self, interpolate_mode="bilinear", **kwargs):
+        super().__init__(input_transform="multiple_select", **kwargs)
+        if interpolate_mode != "bilinear":
+            raise NotImplementedError(f"SegformerHead: interpolate_mode={interpolate_mode!r}: the taps of the reference configs share one size, "
+                                      "only the (identity) bilinear resize is on the HIP path")
+        if (self.norm_cfg or {}).get("type") != "GN":
+            raise NotImplementedError("SegformerHead: only norm_cfg=dict(type='GN') (the reference configs) is on the HIP path")
+        if (self.act_cfg or {}).get("type") != "ReLU":
+            raise NotImplementedError("SegformerHead: only act_cfg=dict(type='ReLU') is on the HIP path")
+        n = len(self.in_channels)
+        assert n == len(self.in_index)
+        if any(c != self.in_channels[0] for c in self.in_channels):
+            raise NotImplementedError("SegformerHead: taps of differing width are not on the HIP path (one batched embedding GEMM)")
+        ch, groups = self.channels, self.norm_cfg.get("num_groups", 32)
+
+        class _ConvModule(nn.Module):  # mmcv ConvModule(norm=GN): conv (no bias) -> gn -> ReLU
+            def __init__(s, cin):
+                super().__init__()
+                s.conv = nn.Conv2d(cin, ch, 1, bias=False)
+                s.gn = nn.GroupNorm(groups, ch)
+
+        self.convs = nn.ModuleList([_ConvModule(c) for c in self.in_channels])
+        self.fusion_conv = _ConvModule(ch * n)
+        self._gn_pack = Fh.NormParamPack()
+
+    @_fp32_on_fp32_taps
+    def forward_tokens(self, fp):
+        cd = compute_dtype()
+        B, P = fp.B, fp.hp * fp.wp
+        n, fc = len(self.convs), self.fusion_conv
+        if fp.xcat.shape[1] != sum(self.in_channels):
+            raise NotImplementedError("SegformerHead: the feature pack does not hold one tap per in_channels entry")
+        gn0 = self.convs[0].gn
+        y = Fh.branch_linear(fp.xcat, [m.conv.weight for m in self.convs])
+        y = Fh.group_norm_cat_act(y, [m.gn.weight for m in self.convs], [m.gn.bias for m in self.convs], B, P, gn0.num_groups, gn0.eps,
+                                  ops.ACT_RELU, cd, pack=self._gn_pack)
+        y = Fh.linear(y, fc.conv.weight, "conv1x1", out_dtype=torch.float32)
+        y = Fh.group_norm_cat_act(y, [fc.gn.weight], [fc.gn.bias], B, P, fc.gn.num_groups, fc.gn.eps, ops.ACT_RELU, cd)
+        y = Fh.dropout(y, self.dropout_ratio, self.training, rows_per_group=P)  # Dropout2d: per (image, channel)
+        lg = Fh.linear(y, self.conv_seg.weight, "conv1x1", bias=self.conv_seg.bias, out_dtype=torch.float32)
+        return lg.view(B, fp.hp, fp.wp, -1)
+
+    def _pack(self, inputs):
+        if not isinstance(inputs, FeatPack):
+            feats = [inputs[i] for i in self.in_index]
+            if any(f.shape[2:] != feats[0].shape[2:] for f in feats):
+                raise NotImplementedError("SegformerHead: taps of differing size (resize_feat / multi-resolution necks) are not on the HIP path")
+        return as_featpack(inputs, self.in_index)
+
+    def forward(self, inputs):
+        return self.forward_tokens(self._pack(inputs)).permute(0, 3, 1, 2)
+
+    def loss(self, inputs, seg_label, return_logits=False):
+        return self._loss_from_lowres(self.forward_tokens(self._pack(inputs)), seg_label, return_logits)
+
+    def predict(self, inputs, batch_img_metas, test_cfg=None):
+        return self.predict_by_feat(self.forward_tokens(self._pack(inputs)), batch_img_metas)
+
+
 # ------------------------------------------------------------------------------------------------ transformer decoder
 class _CrossAttention(nn.Module):
     def __init__(self, query_dim, context_dim=None, heads=8, dim_head=64, dropout=0.0):

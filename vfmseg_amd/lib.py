@@ -126,6 +126,9 @@ SIGNATURES = {
     "vfm_layernorm_bwd": [vp, ci, cl, vp, cl, vp, vp, vp, cl, ci, vp, vp, vp, cl, cl, vp],
     "vfm_groupnorm_fwd": [vp, vp, vp, cf, ci, ci, vp, ci, vp, vp, cl, cl, cl, vp],
     "vfm_groupnorm_bwd": [vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, cl, cl, cl, vp],
+    "vfm_groupnorm_tile_ok": [cl, cl, ci],
+    "vfm_groupnorm_tile_fwd": [vp, vp, vp, cf, ci, ci, vp, ci, vp, cl, cl, cl, vp],
+    "vfm_groupnorm_tile_bwd": [vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, cl, cl, cl, vp],
     "vfm_bn_moments": [vp, cl, cl, vp, vp, vp],
     "vfm_bn_finalize": [vp, cf, vp, vp, vp, cf, cl, vp],
     "vfm_bn_apply": [vp, vp, vp, vp, cf, ci, vp, ci, cl, cl, vp],

@@ -314,6 +314,28 @@ def groupnorm_bwd(dy, x, w, b, stats, groups, act, dx, dw, db, B, P):
     return dx
 
 
+def groupnorm_tile_ok(P, C, groups):
+    """The coverage predicate of the one-launch GroupNorm, asked of the library itself (the C entries check the same function)."""
+    return bool(L.load().vfm_groupnorm_tile_ok(int(P), int(C), int(groups)))
+
+
+def groupnorm_tile_fwd(x, w, b, eps, groups, act, y, stats, B, P):
+    """groupnorm_fwd's contract in one launch; raises (VFM_E_SHAPE) outside groupnorm_tile_ok."""
+    lib = L.load()
+    L.check(lib.vfm_groupnorm_tile_fwd(L.ptr(x), L.ptr(w), L.ptr(b), float(eps), groups, act, L.ptr(y), L.dt_of(y), L.ptr(stats),
+                                       B, P, x.shape[1], L.stream()), "vfm_groupnorm_tile_fwd")
+    return y
+
+
+def groupnorm_tile_bwd(dy, x, w, b, stats, groups, act, dx, dw, db, B, P):
+    lib = L.load()
+    c = x.shape[1]
+    ws = workspace(B * 2 * c, x.device)
+    L.check(lib.vfm_groupnorm_tile_bwd(L.ptr(dy), L.dt_of(dy), L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(stats), groups, act, L.ptr(dx),
+                                       L.ptr(dw), L.ptr(db), L.ptr(ws), B, P, c, L.stream()), "vfm_groupnorm_tile_bwd")
+    return dx
+
+
 def bn_moments(x, sums):
     lib = L.load()
     rows, c = x.shape

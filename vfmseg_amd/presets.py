@@ -183,6 +183,60 @@ def dinov2_hrda(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
     )
 
 
+def segformer_head(embed_dim=1024, channels=256, num_classes=19):
+    """The decode_head block the three SegFormer-head model files share (mmseg SegformerHead on four equal-size taps)."""
+    return dict(
+        type="SegformerHead",
+        in_channels=[embed_dim] * 4,
+        in_index=[0, 1, 2, 3],
+        channels=channels,
+        dropout_ratio=0.1,
+        num_classes=num_classes,
+        norm_cfg=dict(type="GN", num_groups=32),
+        align_corners=False,
+        loss_decode=copy.deepcopy(_CE),
+    )
+
+
+_SLIDE_341 = dict(mode="slide", stride=[341, 341], crop_size=[512, 512])
+
+
+def dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
+    """configs/_base_/models/lora_dinov2_SegFormer.py: LoraBackboneEncoderDecoder (LoRA r=32 on qkv), SegformerHead, 512 / 341 slide test."""
+    return dict(
+        type="LoraBackboneEncoderDecoder",
+        checkpoint=checkpoint,
+        Lora_config=lora_cfg(),
+        data_preprocessor=dict(_PREPROC, size=(512, 512)),
+        backbone=dinov2_backbone(depth, embed_dim, num_heads),
+        decode_head=segformer_head(embed_dim),
+        train_cfg=dict(),
+        test_cfg=dict(_SLIDE_341),
+    )
+
+
+def rein_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
+    """configs/_base_/models/rein_dinov2_segformer.py: EncoderDecoder, frozen DINOv2-L with the Rein adapter, SegformerHead."""
+    cfg = rein_dinov2_linear(depth, embed_dim, num_heads, checkpoint)
+    cfg["decode_head"] = segformer_head(embed_dim)
+    cfg["test_cfg"] = dict(_SLIDE_341)
+    return cfg
+
+
+def frozen_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=None):
+    """configs/_base_/models/dinov2_SegFormer_frozen.py: FrozenBackboneEncoderDecoder - only the SegformerHead trains."""
+    bb = dinov2_backbone(depth, embed_dim, num_heads)
+    bb["init_cfg"] = dict(type="Pretrained", checkpoint=checkpoint)
+    return dict(
+        type="FrozenBackboneEncoderDecoder",
+        data_preprocessor=dict(_PREPROC, size=(512, 512)),
+        backbone=bb,
+        decode_head=segformer_head(embed_dim),
+        train_cfg=dict(),
+        test_cfg=dict(_SLIDE_341),
+    )
+
+
 def optim_cfg():
     embed_multi = dict(lr_mult=1.0, decay_mult=0.0)
     return dict(

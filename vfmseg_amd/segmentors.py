@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import ops
 from .heads import FeatPack
+from .precision import compute_dtype
 from .registry import MODELS
 
 
@@ -383,6 +384,44 @@ class LoraBackboneEncoderDecoder(EncoderDecoder):
 
     def __init__(self, Lora_config, checkpoint=None, backbone=None, **kw):
         super().__init__(backbone=dict(type="LoRABackbone", backbone=backbone, checkpoint=checkpoint, Lora_config=Lora_config), **kw)
+
+
+@MODELS.register_module()
+class FrozenBackboneEncoderDecoder(EncoderDecoder):
+    """rein/models/segmentors/frozen_encoder_decoder.py:19-34: the backbone stays in eval mode, none of its parameters train, and its
+    taps are computed without a graph.  The checkpoint still holds the whole model."""
+
+    def __init__(self, backbone, **kw):
+        super().__init__(backbone=backbone, **kw)
+        # dinov2_SegFormer_frozen.py: the frozen weights arrive through the backbone's init_cfg=dict(type="Pretrained", checkpoint=PATH);
+        # a backbone that reads its own init_cfg (ReinsDinoVisionTransformer) has loaded them already
+        ic = backbone.get("init_cfg") if isinstance(backbone, dict) else None
+        ck = ic.get("checkpoint") if isinstance(ic, dict) else None
+        if ck is not None and getattr(self.backbone, "pretrained", None) is None:
+            if ic.get("type", "Pretrained") != "Pretrained":
+                raise NotImplementedError(f"init_cfg type {ic.get('type')!r}: only dict(type='Pretrained', checkpoint=...) is read")
+            sd = torch.load(ck, map_location="cpu") if isinstance(ck, (str, os.PathLike)) else ck
+            sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+            self.backbone.load_state_dict(sd, strict=True)   # a file whose keys do not match is an error, not an untrained frozen base
+        self.train(self.training)   # frozen from construction on: an optimiser built before the first train() sees no backbone parameter
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.backbone.eval()
+        for p in self.backbone.parameters():
+            p.requires_grad = False
+        return self
+
+    def _tokens(self, jobs):
+        with torch.no_grad():
+            xcat, hp, wp = super()._tokens(jobs)
+            cd = compute_dtype()
+            if self.training and xcat.dtype != cd:
+                # fp16 mode: a backbone that runs without a graph hands out fp32 taps (precision.eval_heads_fp32, meant for predictions);
+                # the train step keeps 16-bit heads, as the reference's autocast does
+                taps = torch.empty(xcat.shape, dtype=cd, device=xcat.device)
+                xcat = ops.cast(xcat, taps)
+        return xcat.detach(), hp, wp
 
 
 @MODELS.register_module()
