@@ -332,8 +332,9 @@ int vfm_resize_bilinear(const void* in, int in_dt, int in_nchw, int B, int Hi, i
                         int out_dt, int out_mode, long out_ld_c, int Hv, int Wv, int y0, int x0, int hc, int wc,
                         float scale_y, float scale_x, void* stream);
 /* bicubic (A=-0.75, align_corners=False, explicit source scales as F.interpolate(scale_factor=...) passes them) on a
- * token-major fp32 map [Hi,Wi,C] -> [Ho,Wo,C]: DINOv2 pos-embed re-interpolation (dino_v2.py:184-215) */
-int vfm_resize_bicubic(const float* in, int Hi, int Wi, int C, float* out, int Ho, int Wo, float scale_y, float scale_x,
+ * token-major fp32 map [Hi,Wi,C] -> [Ho,Wo,C]: DINOv2 pos-embed re-interpolation (dino_v2.py:184-215).  The scales are double and
+ * the source coordinate and the tap weights are computed in double (ABI 5): in float32 they cost more accuracy than the 16 products. */
+int vfm_resize_bicubic(const float* in, int Hi, int Wi, int C, float* out, int Ho, int Wo, double scale_y, double scale_x,
                        void* stream);
 /* nearest (F.interpolate mode='nearest': src=floor(dst*scale)) + crop for int64 label maps (get_lr_seg/get_hr_seg,
  * Ms_VFM_encoder_decoder.py:148-158). in [B,Hi,Wi] -> out [B,hc,wc] of the virtual Hv x Wv map */

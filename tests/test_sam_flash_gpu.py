@@ -6,39 +6,14 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 import vfmseg_amd  # noqa: E402,F401
 from oracle import torch_ref as R  # noqa: E402
 from tests.helpers import rel_err  # noqa: E402
+from tests.sam_window_helpers import window_attention_ref as _ref  # noqa: E402  (the float64 restatement, shared with test_sam_window_*)
 from vfmseg_amd import ops  # noqa: E402
-
-
-def _ref(qkv, bias, rel_h, rel_w, nimg, G, S, H, d):
-    """fp64: [nimg*G*G, 3*H*d] -> [nimg*G*G, H*d]"""
-    C = H * d
-    x = (qkv if qkv.dtype == torch.float64 else qkv.double()).view(nimg, G, G, 3 * C)
-    if S < G:
-        pad = (S - G % S) % S
-        Gp = G + pad
-        xp = bias.double().view(1, 1, 1, 3 * C).expand(nimg, Gp, Gp, 3 * C).clone()    # padded tokens: qkv = bias
-        xp[:, :G, :G] = x
-        w = xp.view(nimg, Gp // S, S, Gp // S, S, 3 * C).permute(0, 1, 3, 2, 4, 5).reshape(-1, S * S, 3, H, d)
-    else:
-        Gp = G
-        w = x.reshape(nimg, S * S, 3, H, d)
-    q, k, v = w.permute(2, 0, 3, 1, 4).unbind(0)                                         # [nb, H, S*S, d]
-    attn = (q * d ** -0.5) @ k.transpose(-2, -1)
-    rh, rw = R.sam_rel_pos(S, S, rel_h.double()), R.sam_rel_pos(S, S, rel_w.double())
-    rq = q.reshape(q.shape[0], H, S, S, d)
-    attn = attn.view(-1, H, S, S, S, S) + torch.einsum("bnhwc,hkc->bnhwk", rq, rh)[..., None] + torch.einsum("bnhwc,wkc->bnhwk", rq, rw)[..., None, :]
-    o = attn.view(-1, H, S * S, S * S).softmax(-1) @ v                                    # [nb, H, S*S, d]
-    o = o.permute(0, 2, 1, 3).reshape(-1, S, S, C)
-    if S < G:
-        o = o.view(nimg, Gp // S, Gp // S, S, S, C).permute(0, 1, 3, 2, 4, 5).reshape(nimg, Gp, Gp, C)[:, :G, :G]
-    return o.reshape(nimg * G * G, C)
 
 
 def _tables(rel, S, JP):

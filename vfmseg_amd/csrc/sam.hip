@@ -285,7 +285,7 @@ __global__ void k_softmax_rows(const float* __restrict__ s, long ld_s, void* __r
   const long row = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* sr = s + row * ld_s;
-  if (n <= 1024) {  // the row lives in registers: one read, one exponential per element
+  if (npad <= 1024) {  // the row lives in registers (16 x 64 columns, pad columns included): one read, one exponential per element
     float v[16];
     float m = -INFINITY;
 #pragma unroll
@@ -510,7 +510,7 @@ __global__ void k_softmax_rows_b(const float* __restrict__ s, long ld_s, void* _
   if (row >= rows) return;
   const bool live = (int)(row % rpb) < valid;
   const float* sr = s + row * ld_s;
-  if (!ds && n <= 1024) {  // forward, row in registers (see k_softmax_rows)
+  if (!ds && npad <= 1024) {  // forward, row in registers (see k_softmax_rows)
     float v[16];
     float m = -INFINITY;
 #pragma unroll
@@ -545,7 +545,7 @@ __global__ void k_softmax_rows_b(const float* __restrict__ s, long ld_s, void* _
     }
     const float inv = 1.f / z;
     for (int c = lane; c < npad; c += 64) st_any(out, row * ld_o + c, out_dt, (live && c < n) ? __expf(sr[c] - m) * inv : 0.f);
-  } else if (n <= 1024) {  // softmax backward with the row of p and of dp in registers
+  } else if (npad <= 1024) {  // softmax backward with the row of p and of dp in registers
     float pv[16], dv[16];
     float dot = 0.f;
 #pragma unroll

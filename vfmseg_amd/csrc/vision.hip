@@ -150,24 +150,28 @@ extern "C" int vfm_resize_bilinear(const void* in, int in_dt, int in_nchw, int B
 // ---------------------------------------------------------------------------------------------------- bicubic
 // ATen upsample_bicubic2d (align_corners=False, A=-0.75): src = scale*(dst+0.5)-0.5 (not clamped), 4x4 taps with indices
 // clamped to the border.  Used once per token grid to re-interpolate the frozen DINOv2 pos-embed (dino_v2.py:184-215).
-__device__ __forceinline__ void cubic_coeffs(float t, float (&w)[4]) {
-  const float A = -0.75f;
-  const float x0 = t + 1.f, x1 = t, x2 = 1.f - t, x3 = 2.f - t;
-  w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-  w[1] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-  w[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
-  w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
+// The source coordinate (from double scales) and the eight tap weights are computed in double and rounded once: in float32 the
+// coordinate is off by up to 2^-23 * Hi (4e-6 of a pixel on the 37-wide pos-embed), and the outer weights (|w| <= 0.07) come out of
+// a Horner form whose terms reach 12, i.e. with an absolute error near 1e-6 each - both far more than the rounding of the 16
+// products (measured against float64: 2.7e-6 before, within 16 * 2^-24 * sum|w||x| after).  The products and sums stay float32.
+__device__ __forceinline__ void cubic_coeffs(double t, float (&w)[4]) {
+  const double A = -0.75;
+  const double x0 = t + 1., x1 = t, x2 = 1. - t, x3 = 2. - t;
+  w[0] = (float)(((A * x0 - 5. * A) * x0 + 8. * A) * x0 - 4. * A);
+  w[1] = (float)(((A + 2.) * x1 - (A + 3.)) * x1 * x1 + 1.);
+  w[2] = (float)(((A + 2.) * x2 - (A + 3.)) * x2 * x2 + 1.);
+  w[3] = (float)(((A * x3 - 5. * A) * x3 + 8. * A) * x3 - 4. * A);
 }
 __global__ void k_resize_bicubic(const float* __restrict__ in, int Hi, int Wi, int C, float* __restrict__ out, int Ho, int Wo,
-                                 float sy, float sx) {
+                                 double sy, double sx) {
   const long total = (long)Ho * Wo * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     long t = i / C;
     const int x = (int)(t % Wo);
     const int y = (int)(t / Wo);
-    const float fy = sy * (y + 0.5f) - 0.5f, fx = sx * (x + 0.5f) - 0.5f;
-    const int iy = (int)floorf(fy), ix = (int)floorf(fx);
+    const double fy = sy * (y + 0.5) - 0.5, fx = sx * (x + 0.5) - 0.5;
+    const int iy = (int)floor(fy), ix = (int)floor(fx);
     float wy[4], wx[4];
     cubic_coeffs(fy - iy, wy);
     cubic_coeffs(fx - ix, wx);
@@ -188,8 +192,8 @@ __global__ void k_resize_bicubic(const float* __restrict__ in, int Hi, int Wi, i
     out[i] = acc;
   }
 }
-extern "C" int vfm_resize_bicubic(const float* in, int Hi, int Wi, int C, float* out, int Ho, int Wo, float scale_y,
-                                  float scale_x, void* stream) {
+extern "C" int vfm_resize_bicubic(const float* in, int Hi, int Wi, int C, float* out, int Ho, int Wo, double scale_y,
+                                  double scale_x, void* stream) {
   const long total = (long)Ho * Wo * C;
   if (total == 0) return VFM_OK;
   const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);

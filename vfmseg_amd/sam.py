@@ -203,7 +203,13 @@ class SamEngine:
             ops.softmax_rows_batched(sc.view(nb * NP, NP), pr.view(nb * NP, NP), Nw, NP, Nw)
             pa = pr[:, :Nw]
         ow = torch.empty(nb, NP, d, dtype=cd, device=dev)
-        ops.gemm(pa, vw, ow[:, :Nw], trans_b=True)                  # P @ V, V consumed in place as the [K, N] operand
+        if is_half(cd) and d % 8:
+            # the 16-bit GEMM takes a [K, N] operand only when N % 8 == 0: such a head width gets V^T [d, NP], K-contiguous
+            vT = torch.empty(nb, d, NP, dtype=cd, device=dev)
+            ops.permute_copy(vw, (0, 2, 1), vT)
+            ops.gemm(pa, vT, ow[:, :Nw])
+        else:
+            ops.gemm(pa, vw, ow[:, :Nw], trans_b=True)              # P @ V, V consumed in place as the [K, N] operand
         ao = torch.empty(nimg * G * G, H * d, dtype=cd, device=dev)
         ops.sam_attn_merge(ow, ao, nimg, G, S, H, d)
         return (ao, pr) if keep else ao
