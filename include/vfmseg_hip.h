@@ -350,6 +350,27 @@ int vfm_unblock(const float* x, float* y, int B, int H, int W, int C, int levels
  *   touch HBM. */
 int vfm_upsample_ce(const float* logits_low, const int64_t* label, int B, int h, int w, int C, int H, int W,
                     int ignore_index, float* loss_parts, int32_t* counts, float* dlogits, void* stream);
+/* vfm_upsample_ce with a per-pixel weight map (mmseg CrossEntropyLoss(weight=seg_weight), reduction 'mean', avg_non_ignore=False;
+ * dacs.py:151-181): weight fp32 [B,H,W] or NULL; loss = sum_valid(weight * -log p[label]) / (B*H*W) and dlogits is scaled the same way.
+ * counts stays UNweighted (a weight-0 pixel with a valid label counts).  weight == NULL is vfm_upsample_ce, bit for bit. (ABI 6) */
+int vfm_upsample_ce_w(const float* logits_low, const int64_t* label, const float* weight, int B, int h, int w, int C, int H, int W,
+                      int ignore_index, float* loss_parts, int32_t* counts, float* dlogits, void* stream);
+/* ---- DACS self-training glue (rein/models/uda/dacs.py:264-299, dacs_transforms.py:96-126): fp32 / int64 / uint8 in both builds ----
+ * vfm_pseudo_label: teacher logits fp32 NHWC [B,h,w,C] (C <= 32) -> bilinear to [H,W] (align_corners=False) -> softmax -> torch.max:
+ *   pseudo_label int64 [B,H,W] (first maximum wins), pseudo_prob fp32 [B,H,W] (may be NULL), count[0] += #pixels with max prob >= thr
+ *   (int32, not reset here).  The full-resolution logits never touch HBM.  pseudo_label 16-byte, pseudo_prob 8-byte aligned. */
+int vfm_pseudo_label(const float* logits_low, int B, int h, int w, int C, int H, int W, float thr, int64_t* pseudo_label,
+                     float* pseudo_prob, int32_t* count, void* stream);
+/* bits uint32 [B,8] |= the set of label values in [0,256) present in image b of label int64 [B,n] (the ignore label 255 is a class here,
+ * as for torch.unique in get_class_masks; other values are skipped).  bits is zeroed by the caller.  Integer OR: order-independent. */
+int vfm_class_presence(const int64_t* label, int B, long n, uint32_t* bits, void* stream);
+/* ClassMix in one pass: mask = (src_label's class is in chosen[b], a 256-bit set as above);
+ *   mixed_img / mixed_label = mask ? source : target / pseudo-label;  mix_weight = mask ? 1 : (row < ignore_top || row >= H - ignore_bottom
+ *   ? 0 : ratio),  ratio = (float)((double)count[0] / (double)total) read on the device (the counter of vfm_pseudo_label; no host sync).
+ * images fp32 [B,3,H,W], labels int64 [B,H,W], mix_weight fp32 [B,H,W], mask uint8 [B,H,W] or NULL. */
+int vfm_class_mix(const float* src_img, const float* tgt_img, const int64_t* src_label, const int64_t* pseudo_label,
+                  const uint32_t* chosen, const int32_t* count, long total, int ignore_top, int ignore_bottom, int B, int H, int W,
+                  float* mixed_img, int64_t* mixed_label, float* mix_weight, uint8_t* mask, void* stream);
 /* After vfm_upsample_ce: loss[0] = scale * sum(loss_parts[0..n)), acc[0] = 100 * counts[0] / (counts[1] + eps) (mmseg `accuracy`
  * over the valid pixels, linear_head.py:95-108), then counts is reset to (0, 0) for the next call. */
 int vfm_ce_finish(const float* loss_parts, long n, float scale, int32_t* counts, float eps, float* loss, float* acc, void* stream);

@@ -268,8 +268,11 @@ extern "C" int vfm_unblock(const float* x, float* y, int B, int H, int W, int C,
 #define CE_CMAX 32
 // WPP = waves per low-res pixel: 1 (small footprints, 4 pixels per block) or 4 (large footprints: the block's four waves
 // split one pixel's candidates and meet in LDS)
-template <int WPP>
-__global__ void __launch_bounds__(256) k_upsample_ce(const float* __restrict__ lg, const int64_t* __restrict__ label, int B, int h,
+// WT: a per-pixel weight map [B,H,W] scales each pixel's loss term and gradient (mmseg CrossEntropyLoss(weight=seg_weight)); the
+// accuracy counters stay unweighted.  WT = false is the kernel as it was (pixw is not read).
+template <int WPP, bool WT>
+__global__ void __launch_bounds__(256) k_upsample_ce(const float* __restrict__ lg, const int64_t* __restrict__ label,
+                                                      const float* __restrict__ pixw, int B, int h,
                                                       int w, int C, int H, int W, int ignore, float sy, float sx,
                                                       float inv_total, float* __restrict__ loss_parts,
                                                       int32_t* __restrict__ counts, float* __restrict__ dlogits) {
@@ -341,7 +344,11 @@ __global__ void __launch_bounds__(256) k_upsample_ce(const float* __restrict__ l
       if (c < C) se += __expf(v[c] - m);
     const float lse = m + __logf(se);
     if (is_valid) {
-      const float g = wy * wx * inv_total;
+      float g = wy * wx * inv_total, wt = 1.f;
+      if constexpr (WT) {
+        wt = pixw[(b * H + hy) * (long)W + hx];
+        g *= wt;
+      }
       const float inv_se = 1.f / se;
 #pragma unroll
       for (int c = 0; c < CE_CMAX; ++c)
@@ -351,7 +358,8 @@ __global__ void __launch_bounds__(256) k_upsample_ce(const float* __restrict__ l
 #pragma unroll
         for (int c = 0; c < CE_CMAX; ++c)
           if (c == (int)lab) vl = v[c];
-        loss += lse - vl;
+        if constexpr (WT) loss += wt * (lse - vl);
+        else loss += lse - vl;
         valid += 1;
         hits += (am == (int)lab) ? 1 : 0;
       }
@@ -421,8 +429,10 @@ __global__ void __launch_bounds__(256) k_upsample_ce(const float* __restrict__ l
 // LDS per block is 25-40 KB and the kernel stays under 128 VGPRs, so four or more blocks share a CU; the redundancy is
 // ((T+1)/T)^2 softmax evaluations per high-res pixel, which is cheap next to the exposed latencies of an under-occupied CU.
 // The block's loss goes to loss_parts[first owned pixel]; its other owned pixels get 0.
-template <int S, int T, int C, int RS>
-__global__ void __launch_bounds__(256) k_upsample_ce_tile(const float* __restrict__ lg, const int64_t* __restrict__ label, int B, int h,
+// WT: as in k_upsample_ce; the weights of a thread's pixels are fetched up front with their labels.
+template <int S, int T, int C, int RS, bool WT>
+__global__ void __launch_bounds__(256) k_upsample_ce_tile(const float* __restrict__ lg, const int64_t* __restrict__ label,
+                                                           const float* __restrict__ pixw, int B, int h,
                                                            int w, int H, int W, int ignore, float inv_total,
                                                            float* __restrict__ loss_parts, int32_t* __restrict__ counts,
                                                            float* __restrict__ dlogits) {
@@ -444,6 +454,7 @@ __global__ void __launch_bounds__(256) k_upsample_ce_tile(const float* __restric
   const int hy_base = S * y0 - S / 2, hx_base = S * x0 - S / 2;
   const float* lb = lg + b * (long)h * w * C;
   int labs[NSTRIP * PPT];  // -1: outside the image / ignored / no pixel
+  float wts[WT ? NSTRIP * PPT : 1];
 #pragma unroll
   for (int k = 0; k < NSTRIP * PPT; ++k) {
     const int i = tid + (k % PPT) * 256;
@@ -452,6 +463,7 @@ __global__ void __launch_bounds__(256) k_upsample_ce_tile(const float* __restric
     if (i < RS * R && hy >= 0 && hy < H && hx >= 0 && hx < W) {
       const int64_t l64 = label[(b * H + hy) * (long)W + hx];
       if (l64 != ignore) lab = (int)l64;
+      if constexpr (WT) wts[k] = pixw[(b * H + hy) * (long)W + hx];
     }
     labs[k] = lab;
   }
@@ -503,8 +515,13 @@ __global__ void __launch_bounds__(256) k_upsample_ce_tile(const float* __restric
         const float inv_se = 1.f / se;
 #pragma unroll
         for (int c = 0; c < C; ++c) v[c] = v[c] * inv_se - (c == lab ? 1.f : 0.f);
+        if constexpr (WT) {
+#pragma unroll
+          for (int c = 0; c < C; ++c) v[c] *= wts[st * PPT + j];
+        }
         if (ly.i0 >= y0 && ly.i0 < y0 + T && lx.i0 >= x0 && lx.i0 < x0 + T) {
-          loss += m + __logf(se) - vl;
+          if constexpr (WT) loss += wts[st * PPT + j] * (m + __logf(se) - vl);
+          else loss += m + __logf(se) - vl;
           valid += 1;
           hits += am == lab ? 1 : 0;
         }
@@ -544,27 +561,250 @@ __global__ void __launch_bounds__(256) k_upsample_ce_tile(const float* __restric
   }
 }
 
-extern "C" int vfm_upsample_ce(const float* logits_low, const int64_t* label, int B, int h, int w, int C, int H, int W,
-                               int ignore_index, float* loss_parts, int32_t* counts, float* dlogits, void* stream) {
+template <bool WT>
+static int upsample_ce_launch(const float* logits_low, const int64_t* label, const float* weight, int B, int h, int w, int C, int H,
+                              int W, int ignore_index, float* loss_parts, int32_t* counts, float* dlogits, void* stream) {
   VFM_CHECK(C > 0 && C <= CE_CMAX, VFM_E_SHAPE, "vfm_upsample_ce: C=%d > %d", C, CE_CMAX);
   VFM_CHECK(H >= h && W >= w, VFM_E_SHAPE, "vfm_upsample_ce: only up-sampling is supported");
   const long npix = (long)B * h * w;
   if (npix == 0) return VFM_OK;
   const bool big = ((long)H * W) >= 64L * h * w;  // footprint (2*scale)^2 >= 256 candidates per low-res pixel
   if (H == 4 * h && W == 4 * w && h % 4 == 0 && w % 4 == 0 && C == 19) {
-    hipLaunchKernelGGL((k_upsample_ce_tile<4, 4, 19, 20>), dim3((unsigned)(B * (h / 4) * (w / 4))), dim3(256), 0, (hipStream_t)stream,
-                       logits_low, label, B, h, w, H, W, ignore_index, 1.0f / ((float)B * H * W), loss_parts, counts, dlogits);
+    hipLaunchKernelGGL((k_upsample_ce_tile<4, 4, 19, 20, WT>), dim3((unsigned)(B * (h / 4) * (w / 4))), dim3(256), 0, (hipStream_t)stream,
+                       logits_low, label, weight, B, h, w, H, W, ignore_index, 1.0f / ((float)B * H * W), loss_parts, counts, dlogits);
   } else if (H == 16 * h && W == 16 * w && C == 19) {
-    hipLaunchKernelGGL((k_upsample_ce_tile<16, 1, 19, 8>), dim3((unsigned)npix), dim3(256), 0, (hipStream_t)stream, logits_low, label, B,
-                       h, w, H, W, ignore_index, 1.0f / ((float)B * H * W), loss_parts, counts, dlogits);
+    hipLaunchKernelGGL((k_upsample_ce_tile<16, 1, 19, 8, WT>), dim3((unsigned)npix), dim3(256), 0, (hipStream_t)stream, logits_low, label,
+                       weight, B, h, w, H, W, ignore_index, 1.0f / ((float)B * H * W), loss_parts, counts, dlogits);
   } else if (big)
-    hipLaunchKernelGGL(k_upsample_ce<4>, dim3((unsigned)npix), dim3(256), 0, (hipStream_t)stream, logits_low, label, B, h, w, C, H, W,
-                       ignore_index, (float)h / (float)H, (float)w / (float)W, 1.0f / ((float)B * H * W), loss_parts, counts,
+    hipLaunchKernelGGL((k_upsample_ce<4, WT>), dim3((unsigned)npix), dim3(256), 0, (hipStream_t)stream, logits_low, label, weight, B, h, w,
+                       C, H, W, ignore_index, (float)h / (float)H, (float)w / (float)W, 1.0f / ((float)B * H * W), loss_parts, counts,
                        dlogits);
   else
-    hipLaunchKernelGGL(k_upsample_ce<1>, dim3(cdiv(npix, 4)), dim3(256), 0, (hipStream_t)stream, logits_low, label, B, h, w, C, H, W,
-                       ignore_index, (float)h / (float)H, (float)w / (float)W, 1.0f / ((float)B * H * W), loss_parts, counts,
+    hipLaunchKernelGGL((k_upsample_ce<1, WT>), dim3(cdiv(npix, 4)), dim3(256), 0, (hipStream_t)stream, logits_low, label, weight, B, h, w,
+                       C, H, W, ignore_index, (float)h / (float)H, (float)w / (float)W, 1.0f / ((float)B * H * W), loss_parts, counts,
                        dlogits);
+  VFM_LAUNCH_CHECK();
+  return VFM_OK;
+}
+
+extern "C" int vfm_upsample_ce(const float* logits_low, const int64_t* label, int B, int h, int w, int C, int H, int W,
+                               int ignore_index, float* loss_parts, int32_t* counts, float* dlogits, void* stream) {
+  return upsample_ce_launch<false>(logits_low, label, nullptr, B, h, w, C, H, W, ignore_index, loss_parts, counts, dlogits, stream);
+}
+
+extern "C" int vfm_upsample_ce_w(const float* logits_low, const int64_t* label, const float* weight, int B, int h, int w, int C, int H,
+                                 int W, int ignore_index, float* loss_parts, int32_t* counts, float* dlogits, void* stream) {
+  if (!weight) return upsample_ce_launch<false>(logits_low, label, nullptr, B, h, w, C, H, W, ignore_index, loss_parts, counts, dlogits, stream);
+  return upsample_ce_launch<true>(logits_low, label, weight, B, h, w, C, H, W, ignore_index, loss_parts, counts, dlogits, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- DACS self-training glue
+// Memory-bound passes over [B,H,W] maps (rein/models/uda/dacs.py:264-299): grids are sized to the chip (grid-stride loops), rows are
+// walked in 16-byte pieces where the width allows it, and everything that is accumulated is an integer.
+static inline int dacs_grid(long work_items) {
+  const long blocks = (work_items + 255) / 256;
+  return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));  // 256 CUs x 8 blocks of 256 threads
+}
+
+// Teacher logits [B,h,w,C] -> bilinear sample at every pixel of [H,W] (the arithmetic of k_upsample_ce), softmax in registers, arg-max
+// with the first maximum winning (torch.max), max probability = 1 / sum(exp(v - max)).  A thread owns two neighbouring pixels of a row
+// so that the int64 labels leave as one 16-byte store when W is even; one integer atomic per block adds the pixels with prob >= thr.
+__global__ void __launch_bounds__(256) k_pseudo_label(const float* __restrict__ lg, int B, int h, int w, int C, int H, int W, float sy,
+                                                       float sx, float thr, int64_t* __restrict__ label, float* __restrict__ prob,
+                                                       int32_t* __restrict__ count) {
+  __shared__ int red[4];
+  const int pw = (W + 1) >> 1;  // pixel pairs per row
+  const long npairs = (long)B * H * pw;
+  const bool vec = (W & 1) == 0;
+  int n_ge = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < npairs; i += (long)gridDim.x * 256) {
+    const int px = (int)(i % pw);
+    const long t = i / pw;
+    const int hy = (int)(t % H);
+    const long b = t / H;
+    const Lerp ly = lerp_idx(hy, sy, h);
+    const float* r0 = lg + (b * h + ly.i0) * (long)w * C;
+    const float* r1 = lg + (b * h + ly.i1) * (long)w * C;
+    int64_t am2[2] = {0, 0};
+    float p2[2] = {0.f, 0.f};
+    for (int k = 0; k < 2; ++k) {
+      const int hx = 2 * px + k;
+      if (hx >= W) break;
+      const Lerp lx = lerp_idx(hx, sx, w);
+      const float *p00 = r0 + (long)lx.i0 * C, *p01 = r0 + (long)lx.i1 * C, *p10 = r1 + (long)lx.i0 * C, *p11 = r1 + (long)lx.i1 * C;
+      float v[CE_CMAX];
+      float m = -INFINITY;
+      int am = 0;
+#pragma unroll
+      for (int c = 0; c < CE_CMAX; ++c) {
+        if (c < C) {
+          v[c] = ly.l0 * (lx.l0 * p00[c] + lx.l1 * p01[c]) + ly.l1 * (lx.l0 * p10[c] + lx.l1 * p11[c]);
+          if (v[c] > m) m = v[c], am = c;
+        }
+      }
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < CE_CMAX; ++c)
+        if (c < C) se += __expf(v[c] - m);
+      am2[k] = am;
+      p2[k] = 1.f / se;
+      n_ge += p2[k] >= thr ? 1 : 0;
+    }
+    const long o = (b * H + hy) * (long)W + 2 * px;
+    if (vec) {
+      *reinterpret_cast<longlong2*>(label + o) = make_longlong2(am2[0], am2[1]);
+      if (prob) *reinterpret_cast<float2*>(prob + o) = make_float2(p2[0], p2[1]);
+    } else {
+      label[o] = am2[0];
+      if (prob) prob[o] = p2[0];
+      if (2 * px + 1 < W) {
+        label[o + 1] = am2[1];
+        if (prob) prob[o + 1] = p2[1];
+      }
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) n_ge += __shfl_xor(n_ge, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n_ge;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n = (red[0] + red[1]) + (red[2] + red[3]);
+    if (n) atomicAdd(count, n);
+  }
+}
+
+extern "C" int vfm_pseudo_label(const float* logits_low, int B, int h, int w, int C, int H, int W, float thr, int64_t* pseudo_label,
+                                float* pseudo_prob, int32_t* count, void* stream) {
+  VFM_CHECK(C > 0 && C <= CE_CMAX, VFM_E_SHAPE, "vfm_pseudo_label: C=%d > %d", C, CE_CMAX);
+  VFM_CHECK(B > 0 && h > 0 && w > 0 && H > 0 && W > 0, VFM_E_SHAPE, "vfm_pseudo_label: empty map");
+  VFM_CHECK(((uintptr_t)pseudo_label & 15) == 0 && ((uintptr_t)pseudo_prob & 7) == 0, VFM_E_ALIGN, "vfm_pseudo_label: outputs must be 16-byte aligned");
+  const long npairs = (long)B * H * ((W + 1) / 2);
+  hipLaunchKernelGGL(k_pseudo_label, dim3(dacs_grid(npairs)), dim3(256), 0, (hipStream_t)stream, logits_low, B, h, w, C, H, W,
+                     (float)h / (float)H, (float)w / (float)W, thr, pseudo_label, pseudo_prob, count);
+  VFM_LAUNCH_CHECK();
+  return VFM_OK;
+}
+
+// bits[b][v >> 5] |= 1 << (v & 31) for every label value v in [0, 256) of image b (255, the ignore label, is a class like any other:
+// torch.unique in get_class_masks).  blockIdx.y = image; a thread ORs into eight registers, the block meets in LDS and issues at most
+// eight integer atomics.
+__global__ void __launch_bounds__(256) k_class_presence(const int64_t* __restrict__ label, long n, uint32_t* __restrict__ bits) {
+  __shared__ uint32_t red[4][8];
+  const int64_t* lb = label + (long)blockIdx.y * n;
+  uint32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto mark = [&](int64_t v) {
+    if (v >= 0 && v < 256) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) m[k] |= ((int)(v >> 5) == k) ? (1u << (v & 31)) : 0u;
+    }
+  };
+  if ((n & 1) == 0) {  // every image starts 16-byte aligned
+    const longlong2* lp = reinterpret_cast<const longlong2*>(lb);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n / 2; i += (long)gridDim.x * 256) {
+      const longlong2 v = lp[i];
+      mark(v.x);
+      mark(v.y);
+    }
+  } else {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) mark(lb[i]);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    for (int o = 32; o > 0; o >>= 1) m[k] |= __shfl_xor(m[k], o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    const uint32_t v = red[0][threadIdx.x] | red[1][threadIdx.x] | red[2][threadIdx.x] | red[3][threadIdx.x];
+    if (v) atomicOr(&bits[blockIdx.y * 8 + threadIdx.x], v);
+  }
+}
+
+extern "C" int vfm_class_presence(const int64_t* label, int B, long n, uint32_t* bits, void* stream) {
+  VFM_CHECK(B > 0 && n > 0, VFM_E_SHAPE, "vfm_class_presence: empty map");
+  VFM_CHECK(((uintptr_t)label & 15) == 0, VFM_E_ALIGN, "vfm_class_presence: label must be 16-byte aligned");
+  int gx = dacs_grid(n / 2) / B;
+  gx = gx < 1 ? 1 : gx;
+  hipLaunchKernelGGL(k_class_presence, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, label, n, bits);
+  VFM_LAUNCH_CHECK();
+  return VFM_OK;
+}
+
+// ClassMix (dacs_transforms.py one_mix, three times) + the pseudo-weight set-up (dacs.py:272-279) in one pass.  mask = the source label's
+// class is in the image's chosen set; mask ? (source image, source label, 1) : (target image, pseudo-label, ratio or 0 in the ignored rows),
+// ratio = (float)((double)count / (double)total) read from the device counter of vfm_pseudo_label.  VEC: four pixels of a row per thread.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_class_mix(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                    const int64_t* __restrict__ src_lbl, const int64_t* __restrict__ ps_lbl,
+                                                    const uint32_t* __restrict__ chosen, const int32_t* __restrict__ count, long total,
+                                                    int ignore_top, int ignore_bottom, int B, int H, int W, float* __restrict__ mixed,
+                                                    int64_t* __restrict__ mixed_lbl, float* __restrict__ weight, uint8_t* __restrict__ mask) {
+  constexpr int V = VEC ? 4 : 1;
+  const float ratio = (float)((double)count[0] / (double)total);
+  const long plane = (long)H * W;
+  const long n = (long)B * plane / V;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long p = i * V;  // pixel index in [B,H,W]; the V pixels share a row (W % 4 == 0 when VEC)
+    const long b = p / plane;
+    const long q = p - b * plane;
+    const int y = (int)(q / W);
+    const float wt_tgt = (y < ignore_top || y >= H - ignore_bottom) ? 0.f : ratio;
+    const uint32_t* set = chosen + b * 8;
+    int64_t sl[V], pl[V];
+    if constexpr (VEC) {
+      const longlong2 a0 = *reinterpret_cast<const longlong2*>(src_lbl + p), a1 = *reinterpret_cast<const longlong2*>(src_lbl + p + 2);
+      const longlong2 c0 = *reinterpret_cast<const longlong2*>(ps_lbl + p), c1 = *reinterpret_cast<const longlong2*>(ps_lbl + p + 2);
+      sl[0] = a0.x, sl[1] = a0.y, sl[2] = a1.x, sl[3] = a1.y;
+      pl[0] = c0.x, pl[1] = c0.y, pl[2] = c1.x, pl[3] = c1.y;
+    } else {
+      sl[0] = src_lbl[p], pl[0] = ps_lbl[p];
+    }
+    bool mk[V];
+    int64_t ol[V];
+    float ow[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      mk[k] = sl[k] >= 0 && sl[k] < 256 && ((set[sl[k] >> 5] >> (sl[k] & 31)) & 1u);
+      ol[k] = mk[k] ? sl[k] : pl[k];
+      ow[k] = mk[k] ? 1.f : wt_tgt;
+    }
+    if constexpr (VEC) {
+      *reinterpret_cast<longlong2*>(mixed_lbl + p) = make_longlong2(ol[0], ol[1]);
+      *reinterpret_cast<longlong2*>(mixed_lbl + p + 2) = make_longlong2(ol[2], ol[3]);
+      *reinterpret_cast<float4*>(weight + p) = make_float4(ow[0], ow[1], ow[2], ow[3]);
+      if (mask) *reinterpret_cast<uchar4*>(mask + p) = make_uchar4(mk[0], mk[1], mk[2], mk[3]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const long o = (b * 3 + c) * plane + q;
+        const float4 s4 = *reinterpret_cast<const float4*>(src + o), t4 = *reinterpret_cast<const float4*>(tgt + o);
+        *reinterpret_cast<float4*>(mixed + o) = make_float4(mk[0] ? s4.x : t4.x, mk[1] ? s4.y : t4.y, mk[2] ? s4.z : t4.z, mk[3] ? s4.w : t4.w);
+      }
+    } else {
+      mixed_lbl[p] = ol[0];
+      weight[p] = ow[0];
+      if (mask) mask[p] = mk[0];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const long o = (b * 3 + c) * plane + q;
+        mixed[o] = mk[0] ? src[o] : tgt[o];
+      }
+    }
+  }
+}
+
+extern "C" int vfm_class_mix(const float* src_img, const float* tgt_img, const int64_t* src_label, const int64_t* pseudo_label,
+                             const uint32_t* chosen, const int32_t* count, long total, int ignore_top, int ignore_bottom, int B, int H,
+                             int W, float* mixed_img, int64_t* mixed_label, float* mix_weight, uint8_t* mask, void* stream) {
+  VFM_CHECK(B > 0 && H > 0 && W > 0 && total > 0, VFM_E_SHAPE, "vfm_class_mix: empty map or total");
+  VFM_CHECK(ignore_top >= 0 && ignore_bottom >= 0, VFM_E_INVAL, "vfm_class_mix: negative ignore rows");
+  const uintptr_t al = (uintptr_t)src_img | (uintptr_t)tgt_img | (uintptr_t)src_label | (uintptr_t)pseudo_label | (uintptr_t)mixed_img |
+                       (uintptr_t)mixed_label | (uintptr_t)mix_weight;
+  const long n = (long)B * H * W;
+  if (W % 4 == 0 && (al & 15) == 0 && ((uintptr_t)mask & 3) == 0)
+    hipLaunchKernelGGL(k_class_mix<true>, dim3(dacs_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, src_img, tgt_img, src_label,
+                       pseudo_label, chosen, count, total, ignore_top, ignore_bottom, B, H, W, mixed_img, mixed_label, mix_weight, mask);
+  else
+    hipLaunchKernelGGL(k_class_mix<false>, dim3(dacs_grid(n)), dim3(256), 0, (hipStream_t)stream, src_img, tgt_img, src_label,
+                       pseudo_label, chosen, count, total, ignore_top, ignore_bottom, B, H, W, mixed_img, mixed_label, mix_weight, mask);
   VFM_LAUNCH_CHECK();
   return VFM_OK;
 }

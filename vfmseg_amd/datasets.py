@@ -384,6 +384,28 @@ class DGDataset:
         return len(self.source)
 
 
+@DATASETS.register_module()
+class UDADataset(DGDataset):
+    """rein/datasets/uda_dataset.py:110-185: pairs {'img': source sample, 'target_img': target sample} for DACS self-training.  The source
+    is drawn as in DGDataset (rare class sampling when configured); under RCS the target index comes from np.random.choice, otherwise both
+    halves follow idx modulo their lengths, and the length is len(source) * len(target).  The reference's class reads `self.target` without
+    ever setting it; it is built here from the `target` config, the evident intent."""
+
+    def __init__(self, source, target, **cfg):
+        super().__init__(source, **cfg)
+        self.target = DATASETS.build(target) if isinstance(target, dict) else target
+
+    def __getitem__(self, idx):
+        if self.rcs_enabled:
+            s1 = self.get_rare_class_sample()
+            i2 = np.random.choice(range(len(self.target)))
+            return {"img": s1, "target_img": self.target[i2]}
+        return {"img": self.source[idx % len(self.source)], "target_img": self.target[idx % len(self.target)]}
+
+    def __len__(self):
+        return len(self.source) * len(self.target)
+
+
 # ------------------------------------------------------------------------------------------------ sampling / loading
 class InfiniteSampler:
     """mmengine InfiniteSampler: an endless stream of shuffled permutations of range(size) from ONE generator seeded alike on
@@ -413,7 +435,10 @@ class InfiniteSampler:
 
 
 def pseudo_collate(batch):
-    """mmengine pseudo_collate for this sample layout: lists, no stacking (SegDataPreProcessor pads and stacks on the GPU)."""
+    """mmengine pseudo_collate for this sample layout: lists, no stacking (SegDataPreProcessor pads and stacks on the GPU).  A UDADataset
+    pair {'img', 'target_img'} is collated half by half (DACS.train_step hands each half to the data preprocessor)."""
+    if "img" in batch[0] and "target_img" in batch[0]:
+        return {k: pseudo_collate([b[k] for b in batch]) for k in ("img", "target_img")}
     return dict(inputs=[b["inputs"] for b in batch], data_samples=[b["data_samples"] for b in batch])
 
 

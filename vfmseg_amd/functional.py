@@ -871,6 +871,30 @@ class UpsampleCEFn(torch.autograd.Function):
         return g, None, None, None
 
 
+class UpsampleCEWeightedFn(torch.autograd.Function):
+    """UpsampleCEFn with a per-pixel weight map fp32 [B,H,W] (mmseg CrossEntropyLoss(weight=seg_weight), reduction 'mean',
+    avg_non_ignore=False: loss = sum_valid(w * -log p[label]) / (B*H*W); the DACS loss on the mixed image, dacs.py:151-181).  The accuracy
+    stays unweighted.  weight=None is UpsampleCEFn bit for bit.  The weight map gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits_low, label, weight, ignore_index, loss_weight):
+        loss, acc, dl = ops.upsample_ce_w_loss_acc(logits_low.contiguous(), label, weight, ignore_index, need_grad=True)
+        ctx.save_for_backward(dl)
+        ctx.lw = loss_weight
+        ctx.mark_non_differentiable(acc)
+        if loss_weight != 1.0:
+            ops.axpby(loss, loss_weight, loss, 0.0)
+        return loss.view(()), acc
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (g,) = ctx.saved_tensors
+        ops.scale_by_device_scalar(g, dloss.contiguous().view(1))
+        if ctx.lw != 1.0:
+            ops.axpby(g, ctx.lw, g, 0.0)
+        return g, None, None, None, None
+
+
 class UpsampleCEAllFn(torch.autograd.Function):
     """UpsampleCEFn with the accuracy of rein/models/heads/utils.py:35-80 (the HRDA head's): 100 * correct / label.numel() - ignored
     pixels stay in the denominator and count as wrong.  Same fused kernel; the raw (hits, valid) counters are finished here."""

@@ -60,11 +60,15 @@ class CrossEntropyLoss(nn.Module):
         return self._loss_name
 
     def forward(self, cls_score, label, weight=None, ignore_index=255, **kw):
-        """cls_score NCHW fp32 at label resolution (API parity); the heads use the fused low-res path instead."""
+        """cls_score NCHW fp32 at label resolution (API parity); the heads use the fused low-res path instead.  weight: per-pixel
+        fp32 [B,H,W] (mmseg's `weight=seg_weight`: the loss term of every pixel is multiplied before the all-pixel mean) or None."""
         lg = torch.empty(cls_score.shape[0], cls_score.shape[2], cls_score.shape[3], cls_score.shape[1],
                          dtype=torch.float32, device=cls_score.device)
         ops.permute_copy(cls_score.detach(), (0, 2, 3, 1), lg)
-        loss, _ = Fh.UpsampleCEFn.apply(lg, label.contiguous(), ignore_index, self.loss_weight)
+        if weight is not None:
+            loss, _ = Fh.UpsampleCEWeightedFn.apply(lg, label.contiguous(), weight.float().contiguous(), ignore_index, self.loss_weight)
+        else:
+            loss, _ = Fh.UpsampleCEFn.apply(lg, label.contiguous(), ignore_index, self.loss_weight)
         return loss
 
 
@@ -106,6 +110,17 @@ class BaseDecodeHead(nn.Module):
             ops.resize_bilinear(logits_nhwc.detach(), False, B, h, w, C, full, 1, (H, W))
             return losses, full
         return losses
+
+    def loss_by_feat(self, seg_logits_nhwc, seg_label, seg_weight=None):
+        """mmseg BaseDecodeHead.loss_by_feat on the low-resolution NHWC logits: {loss_name, acc_seg}.  seg_weight fp32 [B,H,W] weighs every
+        pixel's loss term (DACS's mix_weight); the accuracy is unweighted."""
+        label = (seg_label.squeeze(1) if seg_label.dim() == 4 else seg_label).contiguous()
+        if seg_weight is None:
+            loss, acc = Fh.UpsampleCEFn.apply(seg_logits_nhwc, label, self.ignore_index, self.loss_decode.loss_weight)
+        else:
+            loss, acc = Fh.UpsampleCEWeightedFn.apply(seg_logits_nhwc, label, seg_weight.contiguous(), self.ignore_index,
+                                                      self.loss_decode.loss_weight)
+        return {self.loss_decode.loss_name: loss, "acc_seg": acc}
 
     def predict_by_feat(self, seg_logits_nhwc, batch_img_metas):
         m = batch_img_metas[0]

@@ -1075,6 +1075,117 @@ def upsample_ce_loss_acc(logits_low, label, ignore_index=255, need_grad=True):
     return out[0:1], out[1:2], dl
 
 
+def _ce_w_launch(lib, logits_low, label, weight, ignore_index, parts, counts, dl):
+    B, h, w, Cc = logits_low.shape
+    _, H, W = label.shape
+    assert logits_low.is_contiguous() and label.is_contiguous() and label.dtype == torch.int64 and logits_low.dtype == torch.float32
+    assert weight is None or (weight.dtype == torch.float32 and weight.is_contiguous() and tuple(weight.shape) == tuple(label.shape)), \
+        "weight: fp32 [B,H,W] like the label"
+    L.check(lib.vfm_upsample_ce_w(L.ptr(logits_low), L.ptr(label), L.ptr(weight), B, h, w, Cc, H, W, ignore_index, L.ptr(parts),
+                                  L.ptr(counts), L.ptr(dl), L.stream()), "vfm_upsample_ce_w")
+
+
+def upsample_ce_w(logits_low, label, weight=None, ignore_index=255, need_grad=True, parts_out=None):
+    """upsample_ce with a per-pixel weight map fp32 [B,H,W] (None: the unweighted kernel, bit for bit): loss = sum_valid(w * -log p) / (B*H*W),
+    dlogits scaled alike, counts unweighted.  Returns (loss[1], counts int32[2], dlogits or None).  parts_out: fp32 [B*h*w] that receives
+    the per-low-res-pixel loss parts (tests)."""
+    lib = L.load()
+    B, h, w, _ = logits_low.shape
+    _, H, W = label.shape
+    dev = logits_low.device
+    parts = parts_out if parts_out is not None else torch.empty(B * h * w, dtype=torch.float32, device=dev)
+    assert parts.dtype == torch.float32 and parts.is_contiguous() and parts.numel() == B * h * w
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    dl = torch.empty_like(logits_low) if need_grad else None
+    _ce_w_launch(lib, logits_low, label, weight, ignore_index, parts, counts, dl)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    L.check(lib.vfm_reduce_sum(L.ptr(parts), parts.numel(), 1.0 / (B * H * W), L.ptr(loss), L.stream()), "vfm_reduce_sum")
+    return loss, counts, dl
+
+
+def upsample_ce_w_loss_acc(logits_low, label, weight=None, ignore_index=255, need_grad=True):
+    """The training form of upsample_ce_w (as upsample_ce_loss_acc): (loss[1], acc[1], dlogits)."""
+    lib = L.load()
+    B, h, w, _ = logits_low.shape
+    _, H, W = label.shape
+    dev = logits_low.device
+    counts = _ce_counts.get(dev)
+    if counts is None:
+        counts = _ce_counts[dev] = torch.zeros(2, dtype=torch.int32, device=dev)
+    parts = torch.empty(B * h * w, dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits_low) if need_grad else None
+    _ce_w_launch(lib, logits_low, label, weight, ignore_index, parts, counts, dl)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    eps = float(torch.finfo(torch.float32).eps)
+    L.check(lib.vfm_ce_finish(L.ptr(parts), parts.numel(), 1.0 / (B * H * W), L.ptr(counts), eps, L.ptr(out), L.ptr(out[1:]), L.stream()),
+            "vfm_ce_finish")
+    return out[0:1], out[1:2], dl
+
+
+def pseudo_label(logits_low, size, thr, count, want_prob=False):
+    """Teacher logits fp32 NHWC [B,h,w,C] -> (pseudo_label int64 [B,H,W], pseudo_prob fp32 [B,H,W] or None) at size = (H, W): bilinear
+    (align_corners=False) + softmax + torch.max in registers; count (int32 [1], device) += #pixels with max prob >= thr."""
+    lib = L.load()
+    B, h, w, Cc = logits_low.shape
+    H, W = int(size[0]), int(size[1])
+    assert logits_low.dtype == torch.float32 and logits_low.is_contiguous()
+    assert count.dtype == torch.int32 and count.numel() == 1
+    dev = logits_low.device
+    lab = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    prob = torch.empty(B, H, W, dtype=torch.float32, device=dev) if want_prob else None
+    L.check(lib.vfm_pseudo_label(L.ptr(logits_low), B, h, w, Cc, H, W, float(thr), L.ptr(lab), L.ptr(prob), L.ptr(count), L.stream()),
+            "vfm_pseudo_label")
+    return lab, prob
+
+
+def class_presence(label):
+    """label int64 [B,...] -> uint32-as-int32 [B,8]: the 256-bit set of label values present in each image (255 included)."""
+    lib = L.load()
+    assert label.dtype == torch.int64 and label.is_contiguous()
+    B = label.shape[0]
+    bits = torch.zeros(B, 8, dtype=torch.int32, device=label.device)
+    L.check(lib.vfm_class_presence(L.ptr(label), B, label.numel() // B, L.ptr(bits), L.stream()), "vfm_class_presence")
+    return bits
+
+
+def class_bits_to_lists(bits):
+    """[B,8] bit sets (host or device) -> per image the sorted list of classes (one small device-to-host copy)."""
+    rows = bits.cpu().numpy().view("uint32")
+    return [[k * 32 + j for k in range(8) for j in range(32) if (int(r[k]) >> j) & 1] for r in rows]
+
+
+def class_lists_to_bits(lists, device):
+    """per image an iterable of classes in [0,256) -> int32 [B,8] bit sets on `device`."""
+    import numpy as np
+    arr = np.zeros((len(lists), 8), dtype=np.uint32)
+    for b, cl in enumerate(lists):
+        for c in cl:
+            arr[b, int(c) >> 5] |= np.uint32(1 << (int(c) & 31))
+    return torch.from_numpy(arr.view(np.int32)).to(device)
+
+
+def class_mix(src_img, tgt_img, src_label, pseudo_lbl, chosen, count, total, ignore_top, ignore_bottom, want_mask=False):
+    """One-pass ClassMix (vfm_class_mix).  images fp32 [B,3,H,W]; labels int64 [B,H,W]; chosen int32 [B,8] bit sets; count int32 [1] device
+    counter of pseudo_label, total its denominator.  Returns (mixed_img, mixed_lbl, mix_weight, mask uint8 or None)."""
+    lib = L.load()
+    B, C3, H, W = src_img.shape
+    assert C3 == 3 and tgt_img.shape == src_img.shape and src_img.dtype == tgt_img.dtype == torch.float32
+    assert src_img.is_contiguous() and tgt_img.is_contiguous()
+    for t in (src_label, pseudo_lbl):
+        assert t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (B, H, W)
+    assert chosen.dtype == torch.int32 and chosen.is_contiguous() and tuple(chosen.shape) == (B, 8)
+    assert count.dtype == torch.int32 and count.numel() == 1
+    dev = src_img.device
+    mixed = torch.empty_like(src_img)
+    mlbl = torch.empty_like(src_label)
+    wgt = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    mask = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if want_mask else None
+    L.check(lib.vfm_class_mix(L.ptr(src_img), L.ptr(tgt_img), L.ptr(src_label), L.ptr(pseudo_lbl), L.ptr(chosen), L.ptr(count), int(total),
+                              int(ignore_top), int(ignore_bottom), B, H, W, L.ptr(mixed), L.ptr(mlbl), L.ptr(wgt), L.ptr(mask), L.stream()),
+            "vfm_class_mix")
+    return mixed, mlbl, wgt, mask
+
+
 def _hrda_geo(lr, a, hr, offset, mask_box):
     B, h, w, Cc = lr.shape
     _, ha, wa, _ = a.shape

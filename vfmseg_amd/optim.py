@@ -207,6 +207,26 @@ class OptimWrapper:
         self.optimizer.zero_grad()
         self.iter += 1
 
+    # ---- the piecewise mmengine surface (DACS.train_step: two backward passes, then one step): update_params == backward + step + zero_grad
+    def scale_loss(self, loss):
+        """mmengine OptimWrapper.scale_loss with accumulative_counts == 1: the loss itself."""
+        return loss
+
+    def backward(self, loss, **kw):
+        """Gradients ACCUMULATE into the flat gradient buffer: a second call before step() adds to the first."""
+        self._backward(loss)
+
+    def step(self, **kw):
+        """What update_params does after its backward, up to and including the fused clearing of the gradients."""
+        if self.grad_sync is not None:
+            self.grad_sync()
+        lr = self.scheduler.lr(self.iter) if self.scheduler is not None else None
+        self.optimizer.step(lr, grad_scale=getattr(self.grad_sync, "post_scale", 1.0), zero_grad=True)
+        self.iter += 1
+
+    def zero_grad(self, **kw):
+        self.optimizer.zero_grad()
+
     def get_lr(self):
         return self.optimizer.param_groups[0]["lr"]
 

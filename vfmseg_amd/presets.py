@@ -237,6 +237,28 @@ def frozen_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=N
     )
 
 
+def uda_rein_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=None, work_dir="work_dirs/tmp"):
+    """configs/uda/uda_rein_dinov2_Segformer_512x512.py: DACS self-training around the Rein DINOv2-L + SegformerHead model.  The reference's
+    values, except blur=False and color_jitter_probability=1.0: its colour-jitter / blur branches need kornia, whose import it has
+    commented out (they raise NameError there), and they are not on the HIP path (vfmseg_amd.uda.DACS refuses them)."""
+    cfg = rein_dinov2_segformer(depth, embed_dim, num_heads, checkpoint)
+    cfg.update(
+        type="DACS",
+        alpha=0.999,
+        pseudo_threshold=0.968,
+        pseudo_weight_ignore_top=15,
+        pseudo_weight_ignore_bottom=120,
+        mix="class",
+        blur=False,
+        color_jitter_strength=0.2,
+        color_jitter_probability=1.0,
+        debug_img_interval=500,
+        print_grad_magnitude=False,
+        work_dir=work_dir,
+    )
+    return cfg
+
+
 def optim_cfg():
     embed_multi = dict(lr_mult=1.0, decay_mult=0.0)
     return dict(

@@ -33,6 +33,29 @@ class SyntheticLoader:
         return dict(inputs=imgs, data_samples=[SegDataSample(gt_sem_seg=labs[k]) for k in range(self.bs)])
 
 
+class SyntheticPairLoader:
+    """The synthetic stand-in of a UDADataset stream: {'img': a source batch, 'target_img': a target batch} from two SyntheticLoaders
+    with different seeds (DACS.train_step)."""
+
+    def __init__(self, batch_size, size, rank=0, world=1, seed=0):
+        self.source = SyntheticLoader(batch_size, size, rank, world, seed)
+        self.target = SyntheticLoader(batch_size, size, rank, world, seed + 101)
+
+    @property
+    def i(self):
+        return self.source.i
+
+    @i.setter
+    def i(self, v):
+        self.source.i = self.target.i = v
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return dict(img=next(self.source), target_img=next(self.target))
+
+
 def find_latest_checkpoint(work_dir):
     """mmengine's resume rule: the `last_checkpoint` pointer file if it names an existing file, else the iter_N.pth with the
     largest N (numeric, not lexicographic: iter_8000 < iter_12000)."""
@@ -117,7 +140,8 @@ class Runner:
                           "to read it through vfmseg_amd.datasets)")
         if loader is None:
             size = tuple(cfg.get("crop_size", cfg["model"].get("data_preprocessor", {}).get("size", (1024, 1024))))
-            loader = SyntheticLoader(bs, size, rank, world, seed)
+            paired = cfg["model"].get("type") == "DACS"   # self-training consumes (source, target) pairs
+            loader = (SyntheticPairLoader if paired else SyntheticLoader)(bs, size, rank, world, seed)
         work_dir = cfg.get("work_dir", "./work_dirs/run")
         r = cfg_cls(cfg, model, ow, loader, work_dir, rank, world)
         r.seed = seed
