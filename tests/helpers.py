@@ -258,3 +258,29 @@ def sam_state_dict(depth=32, global_idx=(7, 15, 23, 31), **kw):
         if "lora_" not in k:
             sd[k] = bare_sd[k[len(bb):].replace(".base_layer", "")]
     return sd
+
+
+# Per-element comparison against a float64 reference with a derived bound (the kernel-level float64 suites share these).
+def _half_ulp(mag, dtype):
+    """Half a unit in the last place of `dtype` at magnitude `mag` (an upper bound: eps/2 * mag; half the subnormal spacing below
+    the normal range)."""
+    fi = torch.finfo(dtype)
+    return 0.5 * fi.eps * mag.clamp_min(fi.smallest_normal)
+
+
+def _rounded(ref, b1, dtype):
+    """Bound for a value computed in float32 within b1 of `ref` and then rounded to `dtype`: b1 + half an ulp of the output type at
+    the magnitude of the value that is rounded (at most |ref| + b1)."""
+    return b1 + _half_ulp(ref.abs() + b1, dtype)
+
+
+def _within(name, got, ref, bound):
+    got = got.detach().double().cpu()
+    err = (got - ref).abs()
+    ok = err <= bound                                 # NaN (an element never written) compares False
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, float("inf"), 0.0).double())
+    i = torch.nan_to_num(ratio, nan=float("inf")).argmax()
+    print(f"[{name}] max err {torch.nan_to_num(err, nan=float('inf')).max().item():.2e}, worst element err {err.flatten()[i].item():.2e}"
+          f" vs bound {bound.flatten()[i].item():.2e} (err / bound {ratio.flatten()[i].item():.3f})")
+    assert ok.all(), (name, int((~ok).sum()), err.flatten()[i].item(), bound.flatten()[i].item())
+    return ratio.flatten()[i].item()

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 import vfmseg_amd  # noqa: E402,F401
 from tests import sam_window_helpers as W  # noqa: E402
-from tests.helpers import rel_err  # noqa: E402
+from tests.helpers import _half_ulp, _rounded, _within, rel_err  # noqa: E402,F401
 from vfmseg_amd import ops  # noqa: E402
 
 U24 = 2.0 ** -24
@@ -34,31 +34,6 @@ FLT_MIN = 2.0 ** -126
 
 def _gen(*key):
     return torch.Generator().manual_seed(sum((i + 1) * 7919 * int(k) for i, k in enumerate(key)))
-
-
-def _half_ulp(mag, dtype):
-    """Half a unit in the last place of `dtype` at magnitude `mag` (an upper bound: eps/2 * mag; half the subnormal spacing below
-    the normal range)."""
-    fi = torch.finfo(dtype)
-    return 0.5 * fi.eps * mag.clamp_min(fi.smallest_normal)
-
-
-def _rounded(ref, b1, dtype):
-    """Bound for a value computed in float32 within b1 of `ref` and then rounded to `dtype`: b1 + half an ulp of the output type at
-    the magnitude of the value that is rounded (at most |ref| + b1)."""
-    return b1 + _half_ulp(ref.abs() + b1, dtype)
-
-
-def _within(name, got, ref, bound):
-    got = got.detach().double().cpu()
-    err = (got - ref).abs()
-    ok = err <= bound                                 # NaN (an element never written) compares False
-    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, float("inf"), 0.0).double())
-    i = torch.nan_to_num(ratio, nan=float("inf")).argmax()
-    print(f"[{name}] max err {torch.nan_to_num(err, nan=float('inf')).max().item():.2e}, worst element err {err.flatten()[i].item():.2e}"
-          f" vs bound {bound.flatten()[i].item():.2e} (err / bound {ratio.flatten()[i].item():.3f})")
-    assert ok.all(), (name, int((~ok).sum()), err.flatten()[i].item(), bound.flatten()[i].item())
-    return ratio.flatten()[i].item()
 
 
 def _dtname(dt):

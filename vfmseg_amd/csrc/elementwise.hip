@@ -708,6 +708,17 @@ extern "C" int vfm_swiglu_bwd(const void* h, int h_dt, long ld_h, const void* do
 // eva_02.py:119-160 / 362-369: y = x*cos + rotate_half(x)*sin on the q and k heads of the patch tokens, in place.
 // x: [rows, ld], columns [0, ncols) are consecutive heads of width d; token t = row % np indexes the [np, d] tables.
 // inverse=1 applies the transpose (the gradient of the rotation).
+// One pair, with the contraction spelled out: left to the compiler, a*b - c*d becomes fma(a, b, -(c*d)) in one kernel and
+// fma(-c, d, a*b) in another, and the element-per-thread and the x8 form stop agreeing bit for bit (seen in the fp16 build at d = 64).
+__device__ __forceinline__ void rope_pair(float x0, float x1, float c_0, float c_1, float s_0, float s_1, int inverse, float& y0, float& y1) {
+  if (!inverse) {
+    y0 = fmaf(x0, c_0, -(x1 * s_0));
+    y1 = fmaf(x1, c_1, x0 * s_1);
+  } else {
+    y0 = fmaf(x0, c_0, x1 * s_1);
+    y1 = fmaf(x1, c_1, -(x0 * s_0));
+  }
+}
 __global__ void k_rope(void* __restrict__ x, int dt, long ld, long rows, int np, int ncols, int d, const float* __restrict__ cs,
                        const float* __restrict__ sn, int inverse) {
   const long half = ncols / 2;
@@ -720,13 +731,7 @@ __global__ void k_rope(void* __restrict__ x, int dt, long ld, long rows, int np,
     const float c_0 = cs[(long)t * d + dc], c_1 = cs[(long)t * d + dc + 1];
     const float s_0 = sn[(long)t * d + dc], s_1 = sn[(long)t * d + dc + 1];
     float y0, y1;
-    if (!inverse) {
-      y0 = x0 * c_0 - x1 * s_0;
-      y1 = x1 * c_1 + x0 * s_1;
-    } else {
-      y0 = x0 * c_0 + x1 * s_1;
-      y1 = x1 * c_1 - x0 * s_0;
-    }
+    rope_pair(x0, x1, c_0, c_1, s_0, s_1, inverse, y0, y1);
     st_any(x, r * ld + c0, dt, y0);
     st_any(x, r * ld + c0 + 1, dt, y1);
   }
@@ -741,16 +746,7 @@ __global__ void k_rope_bf16x8(bf16_t* __restrict__ x, long ld, long rows, int np
     F8 v = ld8_bf16(x + r * ld + c0);
     const F8 c = ld8_f32(cs + (long)t * d + dc), sv = ld8_f32(sn + (long)t * d + dc);
 #pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-      const float x0 = v.v[e], x1 = v.v[e + 1];
-      if (!inverse) {
-        v.v[e] = x0 * c.v[e] - x1 * sv.v[e];
-        v.v[e + 1] = x1 * c.v[e + 1] + x0 * sv.v[e + 1];
-      } else {
-        v.v[e] = x0 * c.v[e] + x1 * sv.v[e + 1];
-        v.v[e + 1] = x1 * c.v[e + 1] - x0 * sv.v[e];
-      }
-    }
+    for (int e = 0; e < 8; e += 2) rope_pair(v.v[e], v.v[e + 1], c.v[e], c.v[e + 1], sv.v[e], sv.v[e + 1], inverse, v.v[e], v.v[e + 1]);
     st8_bf16(x + r * ld + c0, v);
   }
 }
