@@ -207,9 +207,14 @@ typedef struct vfm_gemm_desc {
 } vfm_gemm_desc;
 int vfm_gemm(const vfm_gemm_desc* d, void* stream);
 /* tuning / experiment knobs (bench.py --tune KEY=INT).  bf16 GEMM dispatch: "gemm_cfg" forces a tile configuration (-1 = heuristic;
- * 10/18 small tiles, 17 128x128 two-stage, 30/31 ping-pong, 32/33 256x256 ring, 34 128x128 five-chunk ring, 35/36 deeper rings),
- * "gemm_use_pp" bit mask of the kernels the heuristic may pick (default 40), "gemm_split_tail", "gemm_fold_tail", "gemm_bt64",
- * "gemm_batch_tiles".  Unknown keys return VFM_E_INVAL. */
+ * 10/18 small tiles, 16/17 256x256 / 128x128 two-stage, 30/31 ping-pong, 32/33 256x256 ring, 34/52 128x128 five-chunk ring with 8 / 4
+ * waves, 35/36 deeper rings, 39/40 192x256 ring, 51 split-K ring; 37/38/50 only in experimental builds; the retired sweep ids 0-9, 11-15,
+ * 19-29 answer VFM_E_UNSUPPORTED), "gemm_use_pp" bit mask of the kernels the heuristic may pick (default 184), "gemm_use_192" (3),
+ * "gemm_use_ps" (0), "gemm_w44_k" (1024, >= 0), "gemm_deep_tail_k" (0), "gemm_deep_sep_k" (0, >= 0), "gemm_split_tail" (3),
+ * "gemm_fold_tail" (1), "gemm_bt64" (1), "gemm_batch_tiles" (1), "gemm_nt_mb" (0), "pp_dbg", "ps_burst"; attention: "attn_il" (3, 0..3),
+ * "attn_xcd" (1), "attn_short_grid" (256), "attn_fwd64" (0), "attn_lds_pad" (0).  The table is vfmseg_amd/csrc/tune.hip; each knob is
+ * documented where it is defined (vfmseg_amd/csrc/gemm_select.h GemmKnobs, attention_bf16.hip).  Unknown keys and values out of range
+ * return VFM_E_INVAL. */
 int vfm_tune(const char* key, int value);
 
 /* ---- attention -------------------------------------------------------------------------------- */

@@ -584,6 +584,30 @@ def test_gemm_bf16_batched_ragged(cfg):
         ops.tune("gemm_cfg", -1)
 
 
+@pytest.mark.parametrize("cfg", [-1, 10, 18, 17, 34, 35])
+@pytest.mark.parametrize("M,N", [(516, 200), (516, 198), (544, 200), (544, 198), (20, 64)])
+def test_gemm_bf16_tail_modes(cfg, M, N):
+    """The ways the tail rows of M (4 or 32 past a 128-row boundary) can run, at the smallest shapes that reach them (gemm_select.h GemmTail;
+    which plan each case gets is pinned by test_gemm_dispatch_cpu.py): a skinny launch of their own (the rules at this size, configs 10 and
+    18), skinny blocks of the tile launch (17, 34, and 35 with 32 tail rows), inside the regular blocks of the deep ring (35 with 4 tail
+    rows); N = 198 takes the scalar epilogue.  [20 x 64] runs whole on the skinny kernel whatever the config.  Every output element is
+    checked against float64 (NaN-prefilled)."""
+    K = 128 if M == 20 else 256
+    a, b = rnd(M, K, seed=160).bfloat16().to(DEV), rnd(N, K, seed=161).bfloat16().to(DEV)
+    bias = rnd(N, seed=162).to(DEV)
+    ref = a.double() @ b.double().t() + bias.double()
+    ops.tune("gemm_cfg", cfg)
+    try:
+        c = torch.full((M, N), float("nan"), device=DEV)
+        ops.gemm(a, b, c, bias=bias)
+        assert relerr(c, ref) < 2e-5
+        ch = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
+        ops.gemm(a, b, ch, bias=bias)
+        assert relerr(ch.float(), ref) < 1e-2
+    finally:
+        ops.tune("gemm_cfg", -1)
+
+
 @pytest.mark.parametrize("P,M,Q", [(64, 4100, 3072), (64, 4100, 1024), (1024, 2048, 4096), (19, 1000, 256), (200, 333, 128)])
 def test_gemm_bf16_transposed_b(P, M, Q):
     """Weight-gradient form: out[P,Q] = xs^T[P,M] @ y[M,Q], y consumed in place ([K,N] operand), tokens zero-padded."""

@@ -424,7 +424,6 @@ bool vfm_attn_fwd64_launch(const vfm_attn_desc* d, const AttnP& p, hipStream_t s
   if (d->nk_main + d->nk_extra > ATTN_EXTRA_MAX) return false;
   const long blocks = (long)(d->nq_main / 256) * d->B * d->H;
   if (blocks < 192) return false;
-  extern int g_attn_fwd64;
   const dim3 grid(d->nq_main / 256 + (d->nq_extra ? 1 : 0), d->B * d->H);
   constexpr int SMEM = NST * STAGE_BYTES;
   static bool attr = false;

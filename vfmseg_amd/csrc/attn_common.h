@@ -21,6 +21,8 @@ __device__ __forceinline__ long tok_row(int b, int i, int n_main, int B) {
   return i < n_main ? (long)b * n_main + i : (long)B * n_main + b;  // the [cls] token lives after all patch tokens
 }
 
+// the attention knobs of vfm_tune (tune.hip), defined and documented in attention_bf16.hip
+extern int g_attn_short_grid, g_attn_il, g_attn_xcd, g_attn_fwd64, g_attn_lds_pad;
 
 static inline AttnP to_p(const vfm_attn_desc* d) {
   AttnP p;
@@ -33,9 +35,7 @@ static inline AttnP to_p(const vfm_attn_desc* d) {
   p.dq = d->dq; p.dk = d->dk; p.dv = d->dv; p.ld_dq = d->ld_dq; p.ld_dk = d->ld_dk; p.ld_dv = d->ld_dv;
   p.delta = d->delta;
   p.cls_scratch = nullptr;
-  extern int g_attn_xcd;
   p.xcd = g_attn_xcd;
-  extern int g_attn_il;
   p.il = g_attn_il;
   return p;
 }

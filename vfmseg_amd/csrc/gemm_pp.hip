@@ -21,7 +21,7 @@
 //        chunk that is read in interval P+1 has landed in all waves before the barrier that opens P+1.
 //   WAR: the reads issued in interval P are complete (lgkmcnt(0)) in every wave before it leaves interval P+1; a slot is
 //        re-issued at least 3 intervals after its last read (B: read in 2u-1, re-issued in 2u+2; A: 2u, 2u+3).
-#include "gemm_dev.h"
+#include "gemm_launch.h"
 
 namespace {
 constexpr int PP_CH = 16384;
@@ -382,8 +382,12 @@ __global__ void __launch_bounds__(512)
   else epi_scalar<2, 1, 2>(e, zoff, acc, img, lane, m0 + g * 64, n0 + wc * 32, M, N);
 }
 
+// both kernels run 512 threads over more than 64 KiB of LDS: the tail rows of a plan ride along as skinny blocks
+static_assert(kGemmConfigs[gemm_config_index(30)].hosts_tail && PP_SMEM >= 65536, "config table: hosts_tail");
+static_assert(kGemmConfigs[gemm_config_index(31)].hosts_tail && P1_SMEM >= 65536, "config table: hosts_tail");
+
 template <bool VEC>
-static bool launch_pp128_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
+static void launch_pp128_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
   const int tiles_m = cdiv(d->M, 128), tiles_n = cdiv(d->N, 128);
   const long batch = d->batch > 0 ? d->batch : 1;
   static bool attr = false;
@@ -391,23 +395,19 @@ static bool launch_pp128_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm
     (void)hipFuncSetAttribute((const void*)k_gemm_pp128<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, P1_SMEM);
     attr = true;
   }
-  SkinnyTail sk;
-  sk.nblk = 0;
-  const bool fold = tail && batch == 1;
-  if (fold) sk.A = (const bf16_t*)tail->A, sk.lda = tail->sa_m, sk.M = tail->M, sk.nblk = cdiv(tail->N, 32), sk.e = make_epi(tail);
+  const SkinnyTail sk = skinny_tail(tail);
   hipLaunchKernelGGL((k_gemm_pp128<VEC>), dim3(tiles_m * tiles_n + sk.nblk, (unsigned)batch), dim3(512), P1_SMEM, s, (const bf16_t*)d->A,
                      d->sa_m, (const bf16_t*)d->B, d->sb_n, d->M, d->N, d->K, d->stride_a, d->stride_b, d->stride_c, tiles_m, tiles_n,
                      make_epi(d), sk);
-  return fold || !tail;
 }
-bool vfm_gemm_launch_pp128(const vfm_gemm_desc* d, hipStream_t s, bool vec, const vfm_gemm_desc* tail) {
-  if (vec) return launch_pp128_t<true>(d, s, tail);
-  return launch_pp128_t<false>(d, s, tail);
+void vfm_gemm_launch_31(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) {
+  if (p.vec) launch_pp128_t<true>(d, s, tail);
+  else launch_pp128_t<false>(d, s, tail);
 }
 
 int g_pp_dbg = 0;
 template <bool VEC>
-static bool launch_pp256_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
+static void launch_pp256_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
   const int tiles_m = cdiv(d->M, 256), tiles_n = cdiv(d->N, 256);
   const long batch = d->batch > 0 ? d->batch : 1;
   static bool attr = false;
@@ -415,16 +415,12 @@ static bool launch_pp256_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm
     (void)hipFuncSetAttribute((const void*)k_gemm_pp256<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_SMEM);
     attr = true;
   }
-  SkinnyTail sk;
-  sk.nblk = 0;
-  const bool fold = tail && batch == 1;
-  if (fold) sk.A = (const bf16_t*)tail->A, sk.lda = tail->sa_m, sk.M = tail->M, sk.nblk = cdiv(tail->N, 32), sk.e = make_epi(tail);
+  const SkinnyTail sk = skinny_tail(tail);
   hipLaunchKernelGGL((k_gemm_pp256<VEC>), dim3(tiles_m * tiles_n + sk.nblk, (unsigned)batch), dim3(512), PP_SMEM, s, (const bf16_t*)d->A,
                      d->sa_m, (const bf16_t*)d->B, d->sb_n, d->M, d->N, d->K, d->stride_a, d->stride_b, d->stride_c, tiles_m, tiles_n,
                      make_epi(d), g_pp_dbg, sk);
-  return fold || !tail;
 }
-bool vfm_gemm_launch_pp256(const vfm_gemm_desc* d, hipStream_t s, bool vec, const vfm_gemm_desc* tail) {
-  if (vec) return launch_pp256_t<true>(d, s, tail);
-  return launch_pp256_t<false>(d, s, tail);
+void vfm_gemm_launch_30(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) {
+  if (p.vec) launch_pp256_t<true>(d, s, tail);
+  else launch_pp256_t<false>(d, s, tail);
 }

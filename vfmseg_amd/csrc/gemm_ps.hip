@@ -34,7 +34,7 @@
 // an ordinary global load beside LDS-DMA makes hipcc wait vmcnt(0) and drain the ring; bias is DMA'd once per block.
 // All waits are counted by hand (loads, stores and LDS-DMA share one in-order vmcnt); every shape this kernel accepts is
 // tile-aligned, so no store is ever masked off and the counts are exact.
-#include "gemm_dev.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -80,11 +80,9 @@ __device__ __forceinline__ void gelu1(float v, float& g, float& dg) {
 }
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return pack_bf16x2(f32x2{lo, hi}); }
 
-enum { PS_BIAS = 0, PS_GELU_DGELU = 1, PS_MUL = 2, PS_GELU = 3 };   // epilogue kinds (all write bf16 C)
-
+// (the epilogue kinds PS_BIAS .. PS_GELU and PS_PEEL live in gemm_select.h, next to the eligibility test gemm_ps_ok that the selector uses)
 constexpr int PS_NSLOT = 8, PS_UNIT = 16384, PS_RING = PS_NSLOT * PS_UNIT, PS_WAVE_AREA = 4096;
 constexpr int PS_SMEM = PS_RING + 8 * PS_WAVE_AREA;   // 160 KiB
-constexpr int PS_PEEL = 8;                            // slabs per wave tile = K-tiles the previous sub-tile's epilogue rides on
 
 // DBG (timing diagnostics, results garbage; vfm_tune pp_dbg): 1 = no epilogue stores, 2 = no epilogue at all, 4 = no MFMAs, 8 = no operand DMA,
 // 16 = no fragment reads
@@ -421,52 +419,27 @@ __global__ void __launch_bounds__(512) k_gemm_ps(const bf16_t* __restrict__ A, l
 }
 
 template <int EK, int DBG = 0, bool BURST = false>
-bool launch_ps_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail, int per) {
+void launch_ps_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail, int per) {
   const int tiles_m = (int)(d->M / 256), sup_n = (int)(d->N / (128 * per));
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)k_gemm_ps<EK, DBG, BURST>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_SMEM);
     attr = true;
   }
-  SkinnyTail sk;
-  sk.nblk = 0;
-  if (tail) sk.A = (const bf16_t*)tail->A, sk.lda = tail->sa_m, sk.M = tail->M, sk.nblk = cdiv(tail->N, 32), sk.e = make_epi(tail);
+  const SkinnyTail sk = skinny_tail(tail);
   hipLaunchKernelGGL((k_gemm_ps<EK, DBG, BURST>), dim3(tiles_m * sup_n + sk.nblk), dim3(512), PS_SMEM, s, (const bf16_t*)d->A, d->sa_m, (const bf16_t*)d->B,
                      d->sb_n, d->M, d->N, d->K, tiles_m, sup_n, per, make_epi(d), sk);
-  return true;
 }
 
 }  // namespace
 
-// Which epilogue instance serves this descriptor, or -1 (the caller then keeps the tile kernels).
-static int ps_kind(const vfm_gemm_desc* d) {
-  auto a16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
-  if (d->c_dt != VFM_BF16 || d->residual || d->colscale || !a16(d->C) || d->ldc % 8) return -1;
-  const long bm = d->bias_mod > 0 ? d->bias_mod : d->N;
-  if (d->bias && (!a16(d->bias) || bm % 4 || bm < d->N)) return -1;
-  switch (d->ep_mode) {
-    case VFM_EP_NONE: return (d->bias && !d->C2) ? PS_BIAS : -1;
-    case VFM_EP_GELU: return (d->bias && !d->C2) ? PS_GELU : -1;
-    case VFM_EP_GELU_DGELU: return (d->bias && d->C2 && d->c2_dt == VFM_BF16 && a16(d->C2) && d->ldc2 % 8 == 0) ? PS_GELU_DGELU : -1;
-    case VFM_EP_MUL: return (!d->bias && !d->C2 && d->aux && d->aux_dt == VFM_BF16 && a16(d->aux) && d->ld_aux % 8 == 0) ? PS_MUL : -1;
-    default: return -1;
-  }
-}
-
-// per: sub-tiles of 256 x 128 per block (2: a 256 x 256 region).  Shapes: M % 256 == 0, N % (128 per) == 0, K % 64 == 0, K >= 64 * 8 + 64
-// (the previous sub-tile's epilogue rides on the first eight K-tiles), operands contiguous in K, spans < 4 GiB, no batch.
-bool vfm_gemm_ps_ok(const vfm_gemm_desc* d, int per) {
-  if (ps_kind(d) < 0 || d->batch > 1 || per < 1 || per > 2) return false;
-  if (d->sa_k != 1 || d->sb_k != 1 || d->M % 256 || d->N % (128 * per) || d->K % 64 || d->K < 64 * (PS_PEEL + 1)) return false;
-  if ((d->M + 256) * d->sa_m >= (1l << 31) || (d->N + 256) * d->sb_n >= (1l << 31)) return false;
-  if ((d->M + 8) * d->ldc >= (1l << 31) * 2 || (d->aux && (d->M + 8) * d->ld_aux >= (1l << 31))) return false;
-  return ((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && d->sa_m % 8 == 0 && d->sb_n % 8 == 0;
-}
-
-extern int g_pp_dbg;
 int g_ps_burst = 0;   // vfm_tune("ps_burst")
-bool vfm_gemm_launch_ps(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail, int per) {
-  if (g_pp_dbg && ps_kind(d) == PS_GELU_DGELU) {   // timing diagnostics on the fc1 forward instance
+// per: sub-tiles of 256 x 128 per block (2: a 256 x 256 region, config 37; 1: config 38).  The selector asked gemm_ps_ok (gemm_select.h):
+// gemm_ps_kind(d) names one of the four epilogue instances.  512 threads, 160 KiB of LDS: the tail rows ride along as skinny blocks.
+static_assert(kGemmConfigs[gemm_config_index(37)].hosts_tail && kGemmConfigs[gemm_config_index(38)].hosts_tail && PS_SMEM >= 65536, "config table: hosts_tail");
+static void launch_ps(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail, int per) {
+  const int kind = gemm_ps_kind(d);
+  if (g_pp_dbg && kind == PS_GELU_DGELU) {   // timing diagnostics on the fc1 forward instance
     switch (g_pp_dbg) {
       case 1: return launch_ps_t<PS_GELU_DGELU, 1>(d, s, tail, per);
       case 2: return launch_ps_t<PS_GELU_DGELU, 2>(d, s, tail, per);
@@ -477,19 +450,21 @@ bool vfm_gemm_launch_ps(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_de
     }
   }
   if (g_ps_burst) {
-    switch (ps_kind(d)) {
+    switch (kind) {
       case PS_BIAS: return launch_ps_t<PS_BIAS, 0, true>(d, s, tail, per);
       case PS_GELU_DGELU: return launch_ps_t<PS_GELU_DGELU, 0, true>(d, s, tail, per);
       case PS_MUL: return launch_ps_t<PS_MUL, 0, true>(d, s, tail, per);
       case PS_GELU: return launch_ps_t<PS_GELU, 0, true>(d, s, tail, per);
-      default: return false;
+      default: return;
     }
   }
-  switch (ps_kind(d)) {
+  switch (kind) {
     case PS_BIAS: return launch_ps_t<PS_BIAS>(d, s, tail, per);
     case PS_GELU_DGELU: return launch_ps_t<PS_GELU_DGELU>(d, s, tail, per);
     case PS_MUL: return launch_ps_t<PS_MUL>(d, s, tail, per);
     case PS_GELU: return launch_ps_t<PS_GELU>(d, s, tail, per);
-    default: return false;
+    default: return;
   }
 }
+void vfm_gemm_launch_37(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan&, const vfm_gemm_desc* tail) { launch_ps(d, s, tail, 2); }
+void vfm_gemm_launch_38(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan&, const vfm_gemm_desc* tail) { launch_ps(d, s, tail, 1); }

@@ -20,7 +20,7 @@
 //     slot   90            : vmcnt(16), s_barrier   [C]  - tile t+1 has landed for every wave (only tile t+2's pieces may be in flight)
 //     slots  92..122 (even): fragment reads of half 0 of tile t+1 (stage s ^ 1)
 //     end                  : lgkmcnt(0)
-#include "gemm_dev.h"
+#include "gemm_launch.h"
 
 
 
@@ -219,9 +219,8 @@ __global__ void __launch_bounds__(WM_W* WN_W * 64)
   });
 }
 
-extern int g_pp_dbg;
 template <bool VEC, int MI, int NI, int WM_W, int WN_W, int DBG, int STAG = 1>
-static bool launch_v5_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
+static void launch_v5_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
   constexpr int TM = WM_W * MI * 16, TN = WN_W * NI * 16, WAVES = WM_W * WN_W;
   constexpr int RING = 2 * (TM + TN) * 128, EPI = WAVES * 64 * (NI * 16 + 4) * 4, SK = WAVES * 8192;
   constexpr int SMEM = RING > EPI ? (RING > SK ? RING : SK) : (EPI > SK ? EPI : SK);
@@ -232,20 +231,16 @@ static bool launch_v5_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_de
     (void)hipFuncSetAttribute((const void*)k_gemm_v5<VEC, MI, NI, WM_W, WN_W, DBG, STAG>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr = true;
   }
-  SkinnyTail sk;
-  sk.nblk = 0;
-  const bool fold = tail && batch == 1;
-  if (fold) sk.A = (const bf16_t*)tail->A, sk.lda = tail->sa_m, sk.M = tail->M, sk.nblk = cdiv(tail->N, 32), sk.e = make_epi(tail);
+  static_assert(SMEM >= 65536, "config table: hosts_tail");
+  const SkinnyTail sk = skinny_tail(tail);
   hipLaunchKernelGGL((k_gemm_v5<VEC, MI, NI, WM_W, WN_W, DBG, STAG>), dim3(tiles_m * tiles_n + sk.nblk, (unsigned)batch), dim3(WAVES * 64), SMEM, s,
                      (const bf16_t*)d->A, d->sa_m, (const bf16_t*)d->B, d->sb_n, d->M, d->N, d->K, d->stride_a, d->stride_b, d->stride_c,
                      tiles_m, tiles_n, make_epi(d), sk);
-  return fold || !tail;
 }
-// form 0: 256 x 256 tiles, 4 waves (config 50).  K % 64 == 0, K >= 128 (checked by the dispatcher).  Returns whether the tail rows were
-// folded into the launch.
-bool vfm_gemm_launch_v5(const vfm_gemm_desc* d, hipStream_t s, bool vec, const vfm_gemm_desc* tail, int form) {
-  (void)form;
-  if (!vec) return launch_v5_t<false, 8, 8, 2, 2, 0>(d, s, tail);
+// config 50: 256 x 256 tiles, 4 waves.  K % 64 == 0, K >= 128 (checked by the selector); the tail rows of the plan ride along as skinny blocks.
+void vfm_gemm_launch_50(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) {
+  static_assert(kGemmConfigs[gemm_config_index(50)].hosts_tail, "config table: hosts_tail");
+  if (!p.vec) return launch_v5_t<false, 8, 8, 2, 2, 0>(d, s, tail);
   if (g_pp_dbg == 1) return launch_v5_t<true, 8, 8, 2, 2, 1>(d, s, tail);   // diagnostic: main loop only
   if (g_pp_dbg == 2) return launch_v5_t<true, 8, 8, 2, 2, 0, 0>(d, s, tail);   // diagnostic: no stagger
   if (g_pp_dbg == 3) return launch_v5_t<true, 8, 8, 2, 2, 1, 0>(d, s, tail);   // diagnostic: main loop only, no stagger

@@ -23,7 +23,7 @@
 //     step 3: MFMAs (v,s3) | reads (v+1,s0) | DMA chunk 2v+5 [0..3]
 // RAW: K-tile v+1 is first read in step 3, behind beta_v.  WAR: chunks 2v+5 / 2v+6 replace chunks 2v / 2v+1 (K-tile v) and are
 // issued after beta_v.  Every memory instruction sits between two MFMAs: the matrix pipe never waits for an issue.
-#include "gemm_dev.h"
+#include "gemm_launch.h"
 
 // The kernel is generic in the wave tile (MI x NI blocks of 32 x 32) and the wave grid (WM_W x WN_W); the block tile is square
 // (T = WM_W * MI * 32 = WN_W * NI * 32 rows and columns) so that A and B chunks have one size (T rows x 128 B):
@@ -392,11 +392,9 @@ __global__ void __launch_bounds__(WM_W* WN_W * 64, (WM_W * WN_W == 4 && MI == 2 
   }
 }
 
-extern int g_pp_dbg;
-bool vfm_gemm_launch_w4(const vfm_gemm_desc* d, hipStream_t s, bool vec, const vfm_gemm_desc* tail, int form);
 // split-K workspace of a stream: partial sums of up to SPLITK_TILES tiles of 128 x 128 + their counter / flag words (zeroed once: every
 // launch leaves them zero).  One per stream, because launches on different streams may overlap.
-constexpr int SPLITK_TILES = 512;
+constexpr int SPLITK_TILES = GEMM_SPLITK_TILES;
 static SplitK splitk_ws(hipStream_t s) {
   struct Ent { hipStream_t s; SplitK w; };
   static thread_local Ent tab[8];
@@ -414,10 +412,12 @@ static SplitK splitk_ws(hipStream_t s) {
   return w;
 }
 
+// tail: the tail rows of the plan that ride along with this launch - as skinny blocks at the end of the grid, or inside the regular blocks (CLSIN)
 template <bool VEC, int MI, int NI, int WM_W, int WN_W, int P, int DBG, bool CLSIN = false, bool SPLITK = false>
-static bool launch_w4_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
+static void launch_w4_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
   constexpr int TM = WM_W * MI * 32, TN = WN_W * NI * 32, T = TM > TN ? TM : TN, WAVES = WM_W * WN_W;
   constexpr int RING = (2 * P + 1) * T * 128 + (CLSIN ? 8 * 1024 : 0), EPI = WAVES * 64 * (NI * 32 + 4) * 4, SMEM = RING > EPI ? RING : EPI;
+  static_assert(RING >= 65536, "config table: every ring config hosts the tail rows (hosts_tail)");
   const int tiles_m = cdiv(d->M, TM), tiles_n = cdiv(d->N, TN);
   const long batch = d->batch > 0 ? d->batch : 1;
   static bool attr = false;
@@ -427,53 +427,40 @@ static bool launch_w4_t(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_de
   }
   SplitK spk = {nullptr, nullptr, nullptr};
   if constexpr (SPLITK) spk = splitk_ws(s);
-  SkinnyTail sk;
-  sk.nblk = 0;
-  const bool fold = tail && batch == 1 && RING >= 65536 && (!CLSIN || (tail->M <= 8 && tail->sa_k == 1));
-  if (fold) sk.A = (const bf16_t*)tail->A, sk.lda = tail->sa_m, sk.M = tail->M, sk.nblk = cdiv(tail->N, 32), sk.e = make_epi(tail);
+  const SkinnyTail sk = skinny_tail(tail);
   hipLaunchKernelGGL((k_gemm_w4<VEC, MI, NI, WM_W, WN_W, P, DBG, CLSIN, SPLITK>), dim3(tiles_m * tiles_n * (SPLITK ? 2 : 1) + (CLSIN ? 0 : sk.nblk), (unsigned)batch),
                      dim3(WAVES * 64), SMEM, s, (const bf16_t*)d->A, d->sa_m, (const bf16_t*)d->B, d->sb_n, d->M, d->N, d->K, d->stride_a, d->stride_b,
                      d->stride_c, tiles_m, tiles_n, make_epi(d), sk, spk);
-  return fold || !tail;
 }
-// the split-K form of the 128 x 128 ring kernel (see SplitK): K % 128 == 0, K / 2 >= 128, one batch, at most SPLITK_TILES tiles, the vector epilogue
-bool vfm_gemm_splitk_ok(const vfm_gemm_desc* d, bool vec) {
-  return vec && d->batch <= 1 && d->K % 128 == 0 && d->K >= 512 && (long)cdiv(d->M, 128) * cdiv(d->N, 128) <= SPLITK_TILES;
+
+// One ring config of the table: wave tile MI x NI (of 32 x 32), WM_W x WN_W waves, ring of 2 P + 1 chunks.  DBGS: the vfm_tune("pp_dbg")
+// values that have a diagnostic instance of the vector form (1: no epilogue => the MFMAs are dead code too: what is left is the operand
+// stream (DMA + barriers); 4: main loop only (MFMAs live), no epilogue).  Deep rings (P > 2, one block per CU) take the tail rows of a
+// GEMM_TAIL_INSIDE plan inside the regular blocks (CLSIN).
+template <int ID, int MI, int NI, int WM_W, int WN_W, int P, int... DBGS>
+static void launch_ring(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) {
+  static_assert(kGemmConfigs[gemm_config_index(ID)].hosts_tail && kGemmConfigs[gemm_config_index(ID)].deep_ring == (P > 2), "config table: deep_ring");
+  if constexpr (P > 2) {
+    if (p.tail_mode == GEMM_TAIL_INSIDE) {
+      if (p.vec) launch_w4_t<true, MI, NI, WM_W, WN_W, P, 0, true>(d, s, tail);
+      else launch_w4_t<false, MI, NI, WM_W, WN_W, P, 0, true>(d, s, tail);
+      return;
+    }
+  }
+  if (!p.vec) return launch_w4_t<false, MI, NI, WM_W, WN_W, P, 0>(d, s, tail);
+  if (((g_pp_dbg == DBGS && (launch_w4_t<true, MI, NI, WM_W, WN_W, P, DBGS>(d, s, tail), true)) || ...)) return;
+  launch_w4_t<true, MI, NI, WM_W, WN_W, P, 0>(d, s, tail);
 }
-bool vfm_gemm_launch_w4_splitk(const vfm_gemm_desc* d, hipStream_t s, const vfm_gemm_desc* tail) {
-  if (!splitk_ws(s).ws) return vfm_gemm_launch_w4(d, s, true, tail, 2);
-  return launch_w4_t<true, 2, 1, 2, 4, 2, 0, false, true>(d, s, tail);
-}
-// form: 4 = 256x256 / 4 waves, 8 = 256x256 / 8 waves, 6 = 192x256 / 4 waves, 7 = 192x256 / 8 waves, 2 = 128x128 / 8 waves (two blocks per CU), 3 / 5 = 128x128
-// with the seven- / nine-chunk ring (one block per CU).  Returns whether the tail rows were folded into the launch (otherwise
-// the caller runs the skinny kernel).
-bool vfm_gemm_launch_w4(const vfm_gemm_desc* d, hipStream_t s, bool vec, const vfm_gemm_desc* tail, int form) {
-  if (form == 4) {
-    if (!vec) return launch_w4_t<false, 4, 4, 2, 2, 2, 0>(d, s, tail);
-    return g_pp_dbg == 1 ? launch_w4_t<true, 4, 4, 2, 2, 2, 1>(d, s, tail) : launch_w4_t<true, 4, 4, 2, 2, 2, 0>(d, s, tail);
-  }
-  if (form == 9)   // 128 x 128, FOUR waves with 64 x 64 wave tiles (1.0 fragment reads per MFMA instead of the 8-wave form's 1.5), two blocks per CU
-    return vec ? launch_w4_t<true, 2, 2, 2, 2, 2, 0>(d, s, tail) : launch_w4_t<false, 2, 2, 2, 2, 2, 0>(d, s, tail);
-  if (form == 7) return vec ? launch_w4_t<true, 3, 2, 2, 4, 2, 0>(d, s, tail) : launch_w4_t<false, 3, 2, 2, 4, 2, 0>(d, s, tail);
-  if (form == 6) return vec ? launch_w4_t<true, 6, 2, 1, 4, 2, 0>(d, s, tail) : launch_w4_t<false, 6, 2, 1, 4, 2, 0>(d, s, tail);
-  if (form == 8) {
-    if (!vec) return launch_w4_t<false, 4, 2, 2, 4, 2, 0>(d, s, tail);
-    if (g_pp_dbg == 4) return launch_w4_t<true, 4, 2, 2, 4, 2, 4>(d, s, tail);
-    return g_pp_dbg == 1 ? launch_w4_t<true, 4, 2, 2, 4, 2, 1>(d, s, tail) : launch_w4_t<true, 4, 2, 2, 4, 2, 0>(d, s, tail);
-  }
-  // deep rings (one block per CU): tail rows ride inside the regular blocks (CLSIN)
-  const bool clsin = tail && (d->batch <= 1) && tail->M <= 8 && tail->sa_k == 1;
-  if (form == 5) {
-    if (clsin) return vec ? launch_w4_t<true, 2, 1, 2, 4, 4, 0, true>(d, s, tail) : launch_w4_t<false, 2, 1, 2, 4, 4, 0, true>(d, s, tail);
-    return vec ? launch_w4_t<true, 2, 1, 2, 4, 4, 0>(d, s, tail) : launch_w4_t<false, 2, 1, 2, 4, 4, 0>(d, s, tail);
-  }
-  if (form == 3) {
-    if (clsin) return vec ? launch_w4_t<true, 2, 1, 2, 4, 3, 0, true>(d, s, tail) : launch_w4_t<false, 2, 1, 2, 4, 3, 0, true>(d, s, tail);
-    return vec ? launch_w4_t<true, 2, 1, 2, 4, 3, 0>(d, s, tail) : launch_w4_t<false, 2, 1, 2, 4, 3, 0>(d, s, tail);
-  }
-  if (!vec) return launch_w4_t<false, 2, 1, 2, 4, 2, 0>(d, s, tail);
-  if (g_pp_dbg == 1) return launch_w4_t<true, 2, 1, 2, 4, 2, 1>(d, s, tail);   // diagnostic: no epilogue => the MFMAs are dead code too:
-                                                                               // what is left is the operand stream (DMA + barriers)
-  if (g_pp_dbg == 4) return launch_w4_t<true, 2, 1, 2, 4, 2, 4>(d, s, tail);   // diagnostic: main loop only (MFMAs live), no epilogue
-  return launch_w4_t<true, 2, 1, 2, 4, 2, 0>(d, s, tail);
+void vfm_gemm_launch_32(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<32, 4, 4, 2, 2, 2, 1>(d, s, p, tail); }
+void vfm_gemm_launch_33(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<33, 4, 2, 2, 4, 2, 1, 4>(d, s, p, tail); }
+void vfm_gemm_launch_34(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<34, 2, 1, 2, 4, 2, 1, 4>(d, s, p, tail); }
+void vfm_gemm_launch_35(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<35, 2, 1, 2, 4, 3>(d, s, p, tail); }
+void vfm_gemm_launch_36(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<36, 2, 1, 2, 4, 4>(d, s, p, tail); }
+void vfm_gemm_launch_39(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<39, 6, 2, 1, 4, 2>(d, s, p, tail); }
+void vfm_gemm_launch_40(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<40, 3, 2, 2, 4, 2>(d, s, p, tail); }
+void vfm_gemm_launch_52(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) { launch_ring<52, 2, 2, 2, 2, 2>(d, s, p, tail); }
+// the split-K form of the 128 x 128 ring kernel (see SplitK; gemm_splitk_ok in gemm_select.h); without a workspace, the unsplit form (config 34)
+void vfm_gemm_launch_51(const vfm_gemm_desc* d, hipStream_t s, const GemmPlan& p, const vfm_gemm_desc* tail) {
+  if (!splitk_ws(s).ws) return vfm_gemm_launch_34(d, s, p, tail);
+  launch_w4_t<true, 2, 1, 2, 4, 2, 0, false, true>(d, s, tail);
 }
