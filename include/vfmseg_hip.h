@@ -436,6 +436,20 @@ int vfm_slide_finalize(float* preds, const float* count, uint8_t* argmax, int B,
  * pred uint8 [n], label int64 or uint8 [n], both 16-byte aligned; num_classes <= 64. */
 int vfm_confusion_hist(const uint8_t* pred, const void* label, int label_dt, long n, int num_classes, int ignore_index,
                        int64_t* hist, void* stream);
+/* mmseg EncoderDecoder/BaseSegmentor.postprocess_result (1.2.2: remove the padding, undo a test-time flip, resize the logits
+ * bilinearly to ori_shape with align_corners=False, argmax) and the counts rein/dg_metrics.py:46-52 takes from the result, for ONE
+ * image in ONE pass over its output pixels, with no full-resolution logits in memory.
+ * logits: fp32 planes of one batch element, element (c, y, x) of its [Hm, Wm] map at logits[c*plane_stride + y*row_stride + x], C <= 32;
+ * the un-padded window (y0, x0, h, w) is read in place.  flip (0 none, 1 horizontal, 2 vertical) applies to the window.
+ * pred uint8 [oh, ow] = argmax_c (first maximum wins, as vfm_slide_finalize) of the bilinear sample of the (un-flipped) window at
+ * scale (h/oh, w/ow): the arithmetic of vfm_resize_bilinear on a copy of the window, taps clamped to the WINDOW (the padding around
+ * it is never read); h == oh and w == ow passes the values through.
+ * hist != NULL: label int64 or uint8 [oh*ow] and hist int64 [(num_classes+1)*num_classes] += the counts of vfm_confusion_hist
+ * (ignore_index skipped, labels outside [0, num_classes) in row num_classes), exact integer sums; num_classes <= 64.  hist == NULL:
+ * label, label_dt, num_classes and ignore_index are not read.  pred and label 16-byte aligned. */
+int vfm_postprocess_argmax(const float* logits, int C, long plane_stride, long row_stride, int Hm, int Wm, int y0, int x0,
+                           int h, int w, int flip, uint8_t* pred, int oh, int ow, const void* label, int label_dt,
+                           int num_classes, int ignore_index, int64_t* hist, void* stream);
 
 /* ---- optimiser ------------------------------------------------------------------------------------- */
 /* fused multi-tensor AdamW over one flat fp32 buffer (torch.optim.AdamW semantics; groups from

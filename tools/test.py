@@ -4,11 +4,11 @@
 Runs the configured test mode (ms_slide_inference / slide) over the config's test_dataloader.dataset when its data_root exists
 (test pipeline: LoadImageFromFile, Resize(keep_ratio), LoadAnnotations, PackSegInputs -> SegDataPreProcessor -> predict ->
 postprocess to ori_shape), else over synthetic images, and reports mIoU against the labels (mmseg IoUMetric / DGIoUMetric
-semantics) and ms/img."""
+semantics) and ms/img.  One loop for both (vfmseg_amd.evaluation.evaluate); with --launcher pytorch / WORLD_SIZE > 1
+(bash tools/dist_test.sh CONFIG CHECKPOINT GPUS) every rank scores its share and rank 0 prints the summed result."""
 import argparse
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -35,21 +35,20 @@ def main():
     a = ap.parse_args()
     if "LOCAL_RANK" not in os.environ:
         os.environ["LOCAL_RANK"] = str(a.local_rank)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        # Evaluation here is one process (a 1024^2 prediction takes 15 ms): there is no sharded test loop and no reduction of the
-        # confusion matrix, so several ranks would each score the whole test set on the default device and print their own result.
-        raise SystemExit("tools/test.py: distributed evaluation (--launcher %s with WORLD_SIZE=%s) is not implemented; run ONE process "
-                         "(python tools/test.py CONFIG CHECKPOINT)" % (a.launcher, os.environ["WORLD_SIZE"]))
     import numpy as np
     import torch
     import vfmseg_amd  # noqa: F401
     from vfmseg_amd.config import Config, parse_cfg_options
     from vfmseg_amd.registry import METRICS
-    from vfmseg_amd.segmentors import SegDataSample
     from vfmseg_amd.precision import set_compute_dtype
     from vfmseg_amd.registry import MODELS
-    from vfmseg_amd.synth import synth_image, synth_label, synth_like
+    from vfmseg_amd.synth import synth_like
+    from vfmseg_amd import lib as hiplib, parallel
+    from vfmseg_amd.evaluation import dataset_size, evaluate, synthetic_set
     set_compute_dtype(a.dtype)
+    # several ranks (--launcher pytorch / WORLD_SIZE > 1, tools/dist_test.sh): rank r scores the samples r, r + world, ...; one
+    # all-reduce sums the confusion counts and only rank 0 prints
+    rank, world, local = parallel.init_from_env() if (a.launcher == "pytorch" or int(os.environ.get("WORLD_SIZE", "1")) > 1) else (0, 1, int(os.environ["LOCAL_RANK"]))
     cfg = Config.fromfile(a.config)
     cfg.merge_from_dict(parse_cfg_options(a.cfg_options))
     model = MODELS.build(cfg["model"])
@@ -60,7 +59,9 @@ def main():
     if a.backbone:
         sd.update({"backbone." + k: v for k, v in torch.load(a.backbone, map_location="cpu").items()})
     model.load_state_dict(sd, strict=False)
-    torch.cuda.set_device(int(os.environ["LOCAL_RANK"]) % max(torch.cuda.device_count(), 1))
+    dev_index = local % max(torch.cuda.device_count(), 1)
+    torch.cuda.set_device(dev_index)
+    hiplib.set_device_index(dev_index)
     model = model.cuda().eval()
     tta = None
     if a.tta:   # tools/test.py:131-134 swaps in cfg.tta_pipeline / cfg.tta_model (mmseg SegTTAModel: mean of the views' softmax)
@@ -72,11 +73,28 @@ def main():
         if d:
             os.makedirs(d, exist_ok=True)
 
-    def predict(inputs, samples):
-        if tta is None:
-            return model.predict(inputs, samples)
-        from vfmseg_amd.segmentors import predict_tta
-        return predict_tta(model, inputs, samples, tta)
+    class TTAModel:
+        """--tta needs the logits of every view (mean of softmax): predict_tta, then the counts process() takes (metrics.confusion)."""
+        training = False
+        data_preprocessor = model.data_preprocessor
+
+        def eval(self):
+            return self
+
+        def train(self, mode=True):
+            return self
+
+        def parameters(self):
+            return model.parameters()
+
+        def predict_labels(self, inputs, samples, hist=None, num_classes=None, ignore_index=255):
+            from vfmseg_amd.metrics import confusion
+            from vfmseg_amd.segmentors import predict_tta
+            out = predict_tta(model, inputs, samples, tta)
+            for o in out:
+                if hist is not None and hasattr(o, "gt_sem_seg"):
+                    confusion(o.pred_sem_seg.data.squeeze(), o.gt_sem_seg.data.squeeze(), num_classes, ignore_index, out=hist)
+            return out
 
     def dump(out, idx):
         if not (a.out or a.show_dir):
@@ -95,51 +113,26 @@ def main():
     ev = dict(ev[0] if isinstance(ev, (list, tuple)) else ev)
     metric = METRICS.build(ev)      # DGIoUMetric (rein/dg_metrics.py) with the config's dataset_keys, or mmseg's IoUMetric
     keys = list(getattr(metric, "dataset_keys", [])) or ["synthetic"]
-    t = 0.0
     dl = dict(cfg.get("test_dataloader") or cfg.get("val_dataloader") or {})
     ds_cfg = dl.get("dataset")
     root = (ds_cfg.get("source", ds_cfg) if isinstance(ds_cfg, dict) else {}).get("data_root") if ds_cfg else None
     real = a.data == "real" or (a.data == "auto" and root and os.path.isdir(root))
     if real:
         from vfmseg_amd.datasets import DataLoaderIter
-        it = DataLoaderIter(ds_cfg, 1, dl.get("num_workers", 0), shuffle=False, infinite=False)
-        if hasattr(it.dataset, "metainfo"):
-            metric.dataset_meta = dict(classes=it.dataset.metainfo["classes"])
-        n = 0
-        for batch in it.loader:
-            data = model.data_preprocessor(batch, False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = predict(data["inputs"], data["data_samples"])
-            torch.cuda.synchronize()
-            t += time.perf_counter() - t0
-            metric.process(None, out)
-            dump(out, n)
-            n += 1
-            if a.images and n >= a.images:     # only when --images was given: the reference evaluates the whole test_dataloader
-                break
-        res = dict(metric.evaluate(n))
-        res["ms_per_img"] = 1e3 * t / max(n, 1)
-        res["evaluated_samples"] = n
-        res["dataset_size"] = len(it.dataset)
+        data = DataLoaderIter(ds_cfg, 1, dl.get("num_workers", 0), shuffle=False, rank=rank, world=world, infinite=False)
+        if hasattr(data.dataset, "metainfo"):
+            metric.dataset_meta = dict(classes=data.dataset.metainfo["classes"])
+        limit = a.images      # only when --images was given: the reference evaluates the whole test_dataloader
+    else:
+        data, limit = synthetic_set(a.images or 4, tuple(a.size), keys), None
+    res, info = evaluate(model if tta is None else TTAModel(), data, metric, rank, world, limit=limit, on_output=dump)
+    res = dict(res)
+    res["ms_per_img"] = 1e3 * info["seconds"] / max(info["samples"], 1)     # the ranks' summed prediction time over the summed samples
+    res["evaluated_samples"] = info["samples"]
+    if real:
+        res["dataset_size"] = dataset_size(data)
+    if rank == 0:
         print(res)
-        return
-    a.images = a.images or 4
-    for i in range(a.images):
-        img, lab = synth_image(1, tuple(a.size), seed=500 + i).cuda(), synth_label(1, tuple(a.size), seed=500 + i).cuda()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        sample = SegDataSample(gt_sem_seg=lab[0], metainfo=dict(seg_map_path=f"{keys[i % len(keys)]}/synthetic_{i}.png",
-                                                                 ori_shape=tuple(a.size), img_shape=tuple(a.size), padding_size=[0, 0, 0, 0]))
-        out = predict(img, [sample])
-        torch.cuda.synchronize()
-        t += time.perf_counter() - t0
-        metric.process(None, out)
-        dump(out, i)
-    res = dict(metric.evaluate(a.images))
-    res["ms_per_img"] = 1e3 * t / a.images
-    res["evaluated_samples"] = a.images
-    print(res)
 
 
 if __name__ == "__main__":

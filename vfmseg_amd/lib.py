@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvfmseg_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvfmseg_hip_f16.so")
 
 F32, BF16, U8, I64, SPLIT3 = 0, 1, 2, 3, 4
-ABI_VERSION = 6   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points: an older one lacks the symbols
+ABI_VERSION = 7   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax: an older one lacks the symbols
 EP_NONE, EP_GELU, EP_RELU, EP_MUL_GELU_GRAD, EP_MUL, EP_QGELU, EP_MUL_QGELU_GRAD, EP_GELU_DGELU = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_QGELU = 0, 1, 2, 3
 
@@ -175,6 +175,7 @@ SIGNATURES = {
     "vfm_slide_gather": [vp, ci, ci, ci, vp, ci, ci, vp],
     "vfm_conf_gate_windows": [vp, ci, ci, ci, ci, vp, ci, cf, vp, vp],
     "vfm_confusion_hist": [vp, vp, ci, cl, ci, ci, vp, vp],
+    "vfm_postprocess_argmax": [vp, ci, cl, cl] + [ci] * 7 + [vp, ci, ci, vp, ci, ci, ci, vp, vp],
     "vfm_adamw": [vp, vp, vp, vp, cl, vp, vp, vp, ci, cf, cf, cf, cf, ci, cf, ci, ci, vp],
     "vfm_adamw_guarded": [vp, vp, vp, vp, cl, vp, vp, vp, ci, cf, cf, cf, cf, ci, cf, ci, ci, vp, vp, vp],
     "vfm_amp_update": [vp, vp, cf, cf, ci, ci, vp],

@@ -4,7 +4,11 @@ keys plus `mean_<metric>` over `mean_used_keys`).
 
 Per sample one launch of vfm_confusion_hist accumulates the (label, prediction) confusion counts into a device int64 matrix;
 the three areas mmseg's intersect_and_union returns are its diagonal, column sums and row sums.  The host only sees
-(num_classes+1) x num_classes integers per sample group, once, in compute_metrics()."""
+(num_classes+1) x num_classes integers per sample group, once, in compute_metrics().
+
+The evaluation loop (vfmseg_amd.evaluation) uses the running form instead: one device histogram per dataset key (reset_hists / hist_for /
+count_samples), filled by the segmentor's predict_labels in the launch that makes the label map, summed over the ranks as one int64 vector
+(hist_state / load_hist_state) and turned into the same metrics dict by compute_from_hists()."""
 from collections import OrderedDict, defaultdict
 
 import numpy as np
@@ -106,7 +110,10 @@ class IoUMetric:
 
     def _summarise(self, cms):
         nc = self.num_classes
-        total = torch.stack(list(cms)).sum(0).cpu().numpy() if cms else np.zeros((nc + 1) * nc)
+        return self._summarise_total(torch.stack(list(cms)).sum(0).cpu().numpy() if cms else np.zeros((nc + 1) * nc))
+
+    def _summarise_total(self, total):
+        nc = self.num_classes
         ret = total_area_to_metrics(*areas_from_confusion(total, nc), self.metrics, self.nan_to_num, self.beta)
         out = OrderedDict()
         for k, v in ret.items():
@@ -124,6 +131,53 @@ class IoUMetric:
         m = self.compute_metrics(self.results)
         self.results = []
         return {f"{self.prefix}/{k}": v for k, v in m.items()} if self.prefix else m
+
+    # ---- running histograms (vfmseg_amd.evaluation): one device confusion matrix per dataset key instead of one per sample; the
+    # segmentor's predict_labels adds each sample's counts to its key's row on the GPU, the host reads them once per evaluation.
+    @property
+    def hist_keys(self):
+        """The fixed order of the histogram rows."""
+        return ["all"]
+
+    def key_of(self, data_samples):
+        return "all"
+
+    @property
+    def hist_bins(self):
+        return (self.num_classes + 1) * self.num_classes
+
+    def reset_hists(self, device=None):
+        """Zeroed histograms [len(hist_keys), bins] int64 on `device` (None: host, for tests and ranks without a GPU) and sample counts."""
+        self._hists = torch.zeros(len(self.hist_keys), self.hist_bins, dtype=torch.int64, device=device)
+        self._hist_counts = [0] * len(self.hist_keys)
+        return self._hists
+
+    def hist_for(self, data_samples):
+        """(int64 [bins] view of the histogram the batch `data_samples` is filed under, its row index)."""
+        if getattr(self, "_hists", None) is None:
+            raise RuntimeError("reset_hists() first")
+        j = self.hist_keys.index(self.key_of(data_samples))
+        return self._hists[j], j
+
+    def count_samples(self, row, n):
+        self._hist_counts[row] += int(n)
+
+    def hist_state(self):
+        """One int64 vector [K * bins + K]: all histograms, then the per-key sample counts - what the ranks sum."""
+        return torch.cat([self._hists.reshape(-1).cpu(), torch.tensor(self._hist_counts, dtype=torch.int64)])
+
+    def load_hist_state(self, state):
+        K, bins = len(self.hist_keys), self.hist_bins
+        state = torch.as_tensor(state, dtype=torch.int64).cpu()
+        assert state.numel() == K * bins + K, (state.numel(), K, bins)
+        self._hists = state[:K * bins].reshape(K, bins).clone()
+        self._hist_counts = [int(v) for v in state[K * bins:]]
+
+    def compute_from_hists(self):
+        """compute_metrics() of the samples that were accumulated into the histograms."""
+        if self.format_only:
+            return OrderedDict()
+        return self._summarise_total(self._hists[0].cpu().numpy())
 
 
 @METRICS.register_module()
@@ -148,6 +202,37 @@ class DGIoUMetric(IoUMetric):
                     key = k
                     break
             self.results.append([key, self._sample_confusion(s)])
+
+    @property
+    def hist_keys(self):
+        return self.dataset_keys + ["unknown"]
+
+    def key_of(self, data_samples):
+        """The filing rule of process(): the first dataset key contained in the batch's FIRST sample's seg_map_path."""
+        path0 = (_meta(data_samples[0], "seg_map_path", "") or "") if data_samples else ""
+        for k in self.dataset_keys:
+            if k in path0:
+                return k
+        return "unknown"
+
+    def compute_from_hists(self):
+        """compute_metrics() from the per-key histograms; the datasets appear in hist_keys order (compute_metrics: in the order
+        their first sample arrived, which several ranks do not share)."""
+        if self.format_only:
+            return OrderedDict()
+        metrics, to_mean = OrderedDict(), defaultdict(list)
+        total = self._hists.cpu().numpy()
+        self.samples_per_dataset = {k: n for k, n in zip(self.hist_keys, self._hist_counts) if n}
+        for j, key in enumerate(self.hist_keys):
+            if not self._hist_counts[j]:
+                continue
+            for k, v in self._summarise_total(total[j]).items():
+                metrics[f"{key}_{k}"] = v
+                if key in self.mean_used_keys:
+                    to_mean[k].append(v)
+        for k, v in to_mean.items():
+            metrics[f"mean_{k}"] = sum(v) / len(v)
+        return metrics
 
     def compute_metrics(self, results):
         per = defaultdict(list)

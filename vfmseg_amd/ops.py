@@ -1298,6 +1298,31 @@ def confusion_hist(pred_u8, label, hist, num_classes, ignore_index=255):
     return hist
 
 
+def postprocess_argmax(logits, window, flip, out_size, pred=None, label=None, hist=None, num_classes=None, ignore_index=255):
+    """pred uint8 [oh, ow] = argmax over the classes of the window (y0, x0, h, w) of ONE image's fp32 logits [C, H, W] (a view of a
+    batch element of an NCHW map: only its last stride must be 1), un-flipped (flip 0 none, 1 horizontal, 2 vertical) and resized
+    bilinearly to out_size (vfm_postprocess_argmax).  With label (int64 / uint8, oh*ow elements) and hist (int64 [(nc+1)*nc]) the
+    confusion counts of vfm_confusion_hist are added to hist in the same launch."""
+    lib = L.load()
+    assert logits.dim() == 3 and logits.dtype == torch.float32 and logits.stride(2) == 1, (logits.shape, logits.dtype, logits.stride())
+    Cc, Hm, Wm = logits.shape
+    y0, x0, h, w = (int(v) for v in window)
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if pred is None:
+        pred = torch.empty(oh, ow, dtype=torch.uint8, device=logits.device)
+    assert pred.dtype == torch.uint8 and pred.is_contiguous() and pred.numel() == oh * ow
+    ldt = 0
+    if hist is not None:
+        assert hist.dtype == torch.int64 and hist.is_contiguous() and num_classes is not None and hist.numel() == (num_classes + 1) * num_classes
+        if label is not None:
+            assert label.is_contiguous() and label.numel() == oh * ow, (label.shape, (oh, ow))
+            ldt = L.dt_of(label)
+    L.check(lib.vfm_postprocess_argmax(L.ptr(logits), Cc, logits.stride(0), logits.stride(1), Hm, Wm, y0, x0, h, w, int(flip), L.ptr(pred), oh, ow,
+                                       L.ptr(label), ldt, int(num_classes or 0), int(ignore_index), L.ptr(hist), L.stream()),
+            "vfm_postprocess_argmax")
+    return pred
+
+
 def adamw(p, g, m, v, seg_start, seg_lr_mult, seg_wd, lr, betas, eps, step, grad_scale=1.0, zero_grad=False, vec4=False, skip=None, amp_state=None):
     """skip: int32 device tensor [1]; non-zero = leave parameters and moments alone (loss-scaled training: the step's gradients overflowed).
     amp_state: fp32 device tensor [4] {loss scale, growth tracker, steps taken, steps skipped}: un-scale and bias corrections from it."""

@@ -94,6 +94,9 @@ class Runner:
         self.rank, self.world = rank, world
         self.iter = 0
         self.seed = 0
+        self.synthetic = True     # from_cfg: False when the run reads train_dataloader.dataset
+        self._val = None          # (metric, data) of the validation loop, built at the first validation
+        self._best = None
 
     @classmethod
     def from_cfg(cfg_cls, cfg, synthetic=True, device=None):
@@ -145,6 +148,7 @@ class Runner:
         work_dir = cfg.get("work_dir", "./work_dirs/run")
         r = cfg_cls(cfg, model, ow, loader, work_dir, rank, world)
         r.seed = seed
+        r.synthetic = not (ds is not None and not synthetic)
         return r
 
     @staticmethod
@@ -163,15 +167,16 @@ class Runner:
         if self.rank != 0:
             torch.save(self._rng_state(), self._rng_path(path, self.rank))
 
-    def save_checkpoint(self, path):
+    def save_checkpoint(self, path, pointer=True):
         """mmengine CheckpointHook: weights, optimiser state, iteration - plus rank 0's RNG consumers of the hot path (the crop-box
         np.random stream, the dropout / query-mask counter, the loader position) so that a resumed run continues the same
         sample and mask sequence - and a `last_checkpoint` pointer file next to it.  Ranks > 0: save_rank_state."""
         sd = {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
         getattr(self.ow, "sync", lambda: None)()   # AmpOptimWrapper: the last step's overflow verdict (AdamW step count, loss scale)
         torch.save(dict(state_dict=sd, meta=self._rng_state(), optimizer=self.ow.optimizer.state_dict(), optim_wrapper=self.ow.state_dict()), path)
-        with open(os.path.join(os.path.dirname(path) or ".", "last_checkpoint"), "w") as f:
-            f.write(os.path.abspath(path))
+        if pointer:   # (a best_<KEY> copy is not what a resume continues from)
+            with open(os.path.join(os.path.dirname(path) or ".", "last_checkpoint"), "w") as f:
+                f.write(os.path.abspath(path))
 
     def resume(self, path):
         from . import functional as Fh
@@ -205,9 +210,72 @@ class Runner:
         if meta.get("torch_rng") is not None:
             torch.set_rng_state(meta["torch_rng"])
 
+    def _val_setup(self):
+        """(metric, data) of the validation loop: `val_evaluator` (the first of a list, as tools/test.py takes it) and, when the run
+        reads real data, `val_dataloader.dataset` through the test pipeline; otherwise the fixed synthetic set of
+        val_cfg.synthetic_images (4) images that tools/test.py scores, at the training crop size."""
+        if self._val is not None:
+            return self._val
+        from .evaluation import synthetic_set
+        from .registry import METRICS
+        cfg = self.cfg
+        ev = cfg.get("val_evaluator") or dict(type="IoUMetric")
+        metric = METRICS.build(dict(ev[0] if isinstance(ev, (list, tuple)) else ev))
+        dl = dict(cfg.get("val_dataloader") or {})
+        if not self.synthetic and dl.get("dataset") is not None:
+            from .datasets import DATASETS
+            data = DATASETS.build(dl["dataset"]) if isinstance(dl["dataset"], dict) else dl["dataset"]
+            if hasattr(data, "metainfo"):
+                metric.dataset_meta = dict(classes=data.metainfo["classes"])
+        else:
+            size = tuple(cfg.get("crop_size", cfg["model"].get("data_preprocessor", {}).get("size", (1024, 1024))))
+            n = dict(cfg.get("val_cfg") or {}).get("synthetic_images", 4)
+            data = synthetic_set(n, size, list(getattr(metric, "dataset_keys", [])) or ["synthetic"], device="cpu")   # (kept on the host between validations)
+        self._val = (metric, data)
+        return self._val
+
+    def validate(self, log=None):
+        """mmengine's ValLoop after iteration self.iter: every rank scores its shard (vfmseg_amd.evaluation.evaluate: one all-reduce at
+        the end, which also keeps a rank from entering the next training collective while another still validates); rank 0 logs
+        {"iter", "val", "val_samples", "val_time"} and keeps the best checkpoint (default_hooks.checkpoint.save_best).  The random
+        streams training consumes (np.random, the torch generator, the dropout / mask counter) and the train loader are left where
+        they were: the next step is the one a run without validation takes."""
+        from . import functional as Fh
+        from .evaluation import BestCheckpoint, evaluate
+        metric, data = self._val_setup()
+        np_state, torch_state, mask_state = np.random.get_state(), torch.get_rng_state(), dict(Fh._seed_state)
+        cuda_state = torch.cuda.get_rng_state() if torch.cuda.is_available() else None
+        t0 = time.time()
+        try:
+            res, info = evaluate(self.model, data, metric, self.rank, self.world)
+        finally:
+            np.random.set_state(np_state)
+            torch.set_rng_state(torch_state)
+            if cuda_state is not None:
+                torch.cuda.set_rng_state(cuda_state)
+            Fh._seed_state.clear()
+            Fh._seed_state.update(mask_state)
+        rec = {"iter": self.iter, "val": {k: float(v) for k, v in res.items()}, "val_samples": info["samples"], "val_time": time.time() - t0}
+        if self.rank == 0:
+            if log:
+                log.write(json.dumps(rec) + "\n")
+                log.flush()
+            print(rec, flush=True)
+        key = dict(dict(self.cfg.get("default_hooks") or {}).get("checkpoint") or {}).get("save_best")
+        if key:
+            if key not in res:    # every rank holds the same dict: all of them stop
+                raise KeyError(f"save_best={key!r} is not among the validation metrics: {sorted(res)}")
+            if self.rank == 0:
+                if self._best is None:
+                    self._best = BestCheckpoint(key, self.work_dir)
+                self._best.update(res, self.iter, lambda path: self.save_checkpoint(path, pointer=False))
+        return rec
+
     def train(self, max_iters=None, log_interval=50, ckpt_interval=4000):
+        from .evaluation import validation_due
         tc = self.cfg.get("train_cfg", {})
         max_iters = max_iters or tc.get("max_iters", 40000)
+        val_interval, val_begin = tc.get("val_interval"), tc.get("val_begin", 0) or 0
         os.makedirs(self.work_dir, exist_ok=True)
         log = open(os.path.join(self.work_dir, f"scalars_rank{self.rank}.jsonl"), "a") if self.rank == 0 else None
         t0 = time.time()
@@ -227,4 +295,8 @@ class Runner:
             if ckpt_interval and (self.iter % ckpt_interval == 0 or self.iter == max_iters):   # always one at the last iteration
                 ck = os.path.join(self.work_dir, f"iter_{self.iter}.pth")
                 self.save_checkpoint(ck) if self.rank == 0 else self.save_rank_state(ck)
+            if validation_due(self.iter, val_interval, max_iters, val_begin):   # after the checkpoint: mmengine runs its hooks before the val loop
+                tv = time.time()
+                self.validate(log)
+                t0 += time.time() - tv    # (the logged seconds per iteration stay those of training)
         return self.model

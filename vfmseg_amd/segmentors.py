@@ -327,6 +327,71 @@ class EncoderDecoder(nn.Module):
             out.append(ds)
         return out
 
+    @torch.no_grad()
+    def predict_labels(self, inputs, data_samples=None, hist=None, num_classes=None, ignore_index=255):
+        """predict() for callers that need the label map and not the logits (the evaluation loop): the same inference(), then per
+        image ONE vfm_postprocess_argmax launch that reads the un-padded window of the logits in place, undoes the flip, samples at
+        `ori_shape` and takes the argmax - no cropped copy, no full-resolution logits.  Returns samples carrying only `pred_sem_seg`
+        (uint8 [1, oh, ow]).  hist (int64 [(num_classes+1)*num_classes], device): the confusion counts of every sample that has a
+        `gt_sem_seg` are added to it in the same launch.  VFMSEG_POST_FUSED=0: the composition of the existing ops
+        (postprocess_result + metrics.confusion), same values."""
+        if data_samples is not None and len(data_samples) and getattr(data_samples[0], "metainfo", None):
+            metas = [d.metainfo for d in data_samples]
+        else:
+            metas = [dict(ori_shape=inputs.shape[2:], img_shape=inputs.shape[2:], pad_shape=inputs.shape[2:],
+                          padding_size=[0, 0, 0, 0])] * inputs.shape[0]
+        seg_logits = self.inference(inputs, metas)
+        B, C, H, W = seg_logits.shape
+        assert hist is None or num_classes is not None
+        fused = post_fused_default() and C <= 32
+
+        def label_of(ds):
+            gt = getattr(ds, "gt_sem_seg", None) if ds is not None else None
+            if gt is None or hist is None:
+                return None
+            g = (gt if torch.is_tensor(gt) else gt.data).to(seg_logits.device)
+            return (g if g.dtype in (torch.uint8, torch.int64) else g.long()).contiguous()
+
+        out = []
+        if not fused:
+            from .metrics import confusion
+            for ds in self.postprocess_result(seg_logits, data_samples, metas):
+                pred = ds.pred_sem_seg.data
+                res = SegDataSample(metainfo=ds.metainfo)
+                if hasattr(ds, "gt_sem_seg"):
+                    res.gt_sem_seg = ds.gt_sem_seg
+                res.pred_sem_seg = PixelData(pred)
+                lab = label_of(ds)
+                if lab is not None:
+                    confusion(pred, lab, num_classes, ignore_index, out=hist)
+                out.append(res)
+            return out
+        for i in range(B):
+            m = metas[i] if metas else {}
+            pl, pr, pt, pb = [int(v) for v in m.get("img_padding_size", m.get("padding_size", [0, 0, 0, 0]))]
+            h, w = H - pt - pb, W - pl - pr
+            flip = 0
+            if m.get("flip"):
+                fd = m.get("flip_direction", "horizontal")
+                assert fd in ("horizontal", "vertical")
+                flip = 1 if fd == "horizontal" else 2
+            oh, ow = tuple(m.get("ori_shape", (h, w)))[:2]
+            ds = data_samples[i] if data_samples else None
+            lab = label_of(ds)
+            pred = ops.postprocess_argmax(seg_logits[i], (pt, pl, h, w), flip, (oh, ow), label=lab, hist=None if lab is None else hist,
+                                          num_classes=num_classes, ignore_index=ignore_index)
+            res = SegDataSample(metainfo=m)
+            if ds is not None and hasattr(ds, "gt_sem_seg"):
+                res.gt_sem_seg = ds.gt_sem_seg
+            res.pred_sem_seg = PixelData(pred.view(1, oh, ow))
+            out.append(res)
+        return out
+
+
+def post_fused_default():
+    """VFMSEG_POST_FUSED (A/B knob, default 1): predict_labels runs vfm_postprocess_argmax; 0 composes the existing ops."""
+    return os.environ.get("VFMSEG_POST_FUSED", "1") != "0"
+
 
 def tta_views(tta_pipeline):
     """(ratio, flip) views of an mmseg `tta_pipeline` (the TestTimeAug entry: a list of Resize alternatives x a list of RandomFlip
