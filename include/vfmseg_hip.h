@@ -403,6 +403,23 @@ int vfm_reduce_sum(const float* x, long n, float scale, float* out, void* stream
  * (x - mean[c]) / std[c] (mean3 / std3: host arrays of 3, given in the OUTPUT channel order), right/bottom padding with pad_val. */
 int vfm_preprocess_u8(const uint8_t* img, int H, int W, float* out, int Hp, int Wp, const float* mean3, const float* std3,
                       int bgr_to_rgb, float pad_val, void* stream);
+/* Training augmentation on the device: the transform chain of vfmseg_amd/datasets.py after the decode - Resize (bilinear,
+ * F.interpolate(align_corners=False) in float32, rounded half to even) -> RandomCrop -> RandomFlip -> PhotoMetricDistortion - followed by
+ * vfm_preprocess_u8's channel swap, normalisation and padding, in one launch per sample.  The host draws; the plan carries the outcome. */
+typedef struct vfm_augment_plan {
+  int resize_h, resize_w;             /* target of the resize; 0, 0: no resize */
+  int crop_y, crop_x, crop_h, crop_w; /* the crop window inside the resized image (the whole image when the chain has no crop) */
+  int flip;                           /* 0 none, 1 horizontal, 2 vertical: of the crop window */
+  int wide;                           /* PhotoMetricDistortion._convert in float32 (0: what numpy computes with a Python-float parameter) or float64 (1) */
+  int brightness_on, contrast_on;     /* contrast_on: 0 off, 1 before the colour steps (mode 1), 2 after them (mode 0) */
+  int saturation_on, hue_on, hue_delta;
+  double brightness_beta, contrast_alpha, saturation_alpha;
+} vfm_augment_plan;
+/* img: uint8 HWC [Hs, Ws, 3] as decoded (device memory); out: fp32 [3, Hp, Wp], the crop at the top left, the rest pad_val; plan, mean3,
+ * std3: HOST memory.  Every source read is clamped into the image; a crop box outside the resize target, or larger than the output,
+ * returns VFM_E_SHAPE before any launch. */
+int vfm_augment_u8(const uint8_t* img, int Hs, int Ws, const vfm_augment_plan* plan, float* out, int Hp, int Wp, const float* mean3,
+                   const float* std3, int bgr_to_rgb, float pad_val, void* stream);
 /* confidence gate (Ms_VFM_encoder_decoder.py:446-448): frac[0] = mean_pixels( max softmax(logits) > thr ) over the
  * window of an NCHW map [B,C,H,W]; counts int32 [1] zeroed by the caller */
 int vfm_conf_gate(const float* logits, int B, int C, int H, int W, int y0, int x0, int hc, int wc, float thr,

@@ -118,8 +118,9 @@ def main():
     root = (ds_cfg.get("source", ds_cfg) if isinstance(ds_cfg, dict) else {}).get("data_root") if ds_cfg else None
     real = a.data == "real" or (a.data == "auto" and root and os.path.isdir(root))
     if real:
-        from vfmseg_amd.datasets import DataLoaderIter
-        data = DataLoaderIter(ds_cfg, 1, dl.get("num_workers", 0), shuffle=False, rank=rank, world=world, infinite=False)
+        from vfmseg_amd.datasets import DataLoaderIter, device_augment_on
+        data = DataLoaderIter(ds_cfg, 1, dl.get("num_workers", 0), shuffle=False, rank=rank, world=world, infinite=False,
+                              device_augment=device_augment_on(dl))   # test_dataloader.device_augment / VFMSEG_AUG_DEVICE
         if hasattr(data.dataset, "metainfo"):
             metric.dataset_meta = dict(classes=data.dataset.metainfo["classes"])
         limit = a.images      # only when --images was given: the reference evaluates the whole test_dataloader

@@ -22,7 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=f
 # cost more issue cycles there than the two scalar adds they replace
 EXTRA = {"attention_fwd64.hip": ["-fno-slp-vectorize"],
          # gemm_ps.hip runs its epilogue arithmetic between the MFMAs of the next sub-tile: packed f32 VALU is an anti-lever there
-         "gemm_ps.hip": ["-fno-slp-vectorize"]}
+         "gemm_ps.hip": ["-fno-slp-vectorize"],
+         # augment.hip reproduces numpy's separately rounded float32 / float64 operations bit for bit: no fused multiply-add
+         "augment.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

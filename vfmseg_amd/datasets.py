@@ -2,7 +2,9 @@
 of `configs/_base_/datasets/*.py` (LoadImageFromFile, LoadAnnotations, Resize, RandomCrop, RandomFlip, PhotoMetricDistortion,
 PackSegInputs), the rare-class-sampling wrapper `DGDataset` (rein/datasets/uda_dataset.py:15-107) and an infinite, rank-sharded
 loader (mmengine InfiniteSampler + pseudo_collate).  Host-side numpy / PIL code: it feeds `SegDataPreProcessor`'s uint8 path
-(one HIP kernel per sample for channel swap + normalise + pad), nothing here touches the GPU.
+(one HIP kernel per sample for channel swap + normalise + pad), nothing here touches the GPU.  With `device_augment` the chain runs in
+plan mode (Compose(device=True)): the host still makes every random draw and handles the label, and hands the decoded image plus an
+`aug_plan` to SegDataPreProcessor, whose kernel vfm_augment_u8 resizes, crops, flips and distorts it.
 
 The transform semantics are third-party (mmsegmentation 1.2.2 / mmcv 2.1.0, not under /root/reference): restated from their
 published behaviour, with two deliberate, documented deviations forced by this image (no OpenCV): images are decoded with PIL
@@ -72,7 +74,41 @@ def _resize(arr, size_hw, mode):
     return (o[0] if arr.ndim == 2 else o.permute(1, 2, 0)).contiguous().numpy()
 
 
+def nearest_index(n_in, n_out):
+    """Source index of every output position of F.interpolate(mode="nearest") on a float tensor: min(floor(dst * scale), in - 1) with
+    scale = (float)in / out in float32 (ATen's nearest_idx) - the label resize of plan mode, one axis."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    return np.minimum(np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64), n_in - 1)
+
+
+_CONVERT_WIDE = None
+
+
+def convert_is_wide():
+    """The width in which PhotoMetricDistortion._convert computes, given what __call__ really hands it: the result of np.random.uniform.
+    That is a Python float, which leaves a float32 array float32 under numpy 1 (value-based casting) and numpy 2 (weak scalar) alike; a
+    numpy whose uniform returned np.float64 would compute in float64 under numpy 2.  Probed once with _convert itself and a private
+    generator (np.random is not touched), not assumed; the device kernel has both widths."""
+    global _CONVERT_WIDE
+    if _CONVERT_WIDE is None:
+        drawn = np.random.RandomState(0).uniform(1.0, 1.0)
+        _CONVERT_WIDE = bool((np.zeros(1, np.float32) * drawn + drawn).dtype == np.float64)
+    return _CONVERT_WIDE
+
+
+def device_augment_on(dataloader_cfg):
+    """`<x>_dataloader.device_augment` (default off); VFMSEG_AUG_DEVICE=1|0 overrides the config."""
+    env = os.environ.get("VFMSEG_AUG_DEVICE")
+    if env in ("0", "1"):
+        return env == "1"
+    return bool((dataloader_cfg or {}).get("device_augment", False))
+
+
 # ------------------------------------------------------------------------------------------------ transforms
+# Every transform has two entries.  __call__ is the host chain.  plan() is the device form (Compose(device=True)): it consumes np.random
+# exactly as __call__ does - same calls, same order, same arguments - and records parameters in results["aug_plan"] instead of touching the
+# image; label maps are small and still travel on the host.  STAGE orders the chain the device kernel computes (vfm_augment_u8: resize,
+# crop, flip, photometric): each staged transform at most once, stages ascending.
 @TRANSFORMS.register_module()
 class LoadImageFromFile:
     """mmcv LoadImageFromFile: decoded image HxWx3 uint8 in BGR order (cv2 backend), img_shape / ori_shape."""
@@ -81,15 +117,31 @@ class LoadImageFromFile:
         self.to_float32 = to_float32
 
     def __call__(self, results):
-        from PIL import Image
-        with Image.open(results["img_path"]) as im:
-            img = np.asarray(im.convert("RGB"))[..., ::-1]
-        img = np.ascontiguousarray(img)
+        # plan mode: BaseSegDataset keeps the last decoded files.  No transform writes into them, and the sample's `inputs` tensor ALIASES
+        # the cached image (PackSegInputs.plan): a consumer must not write into `inputs` in place (SegDataPreProcessor only reads it)
+        cache = results.get("_decoded")
+        img = None if cache is None else cache.get(("img", results["img_path"]))
+        if img is None:
+            from PIL import Image
+            with Image.open(results["img_path"]) as im:
+                img = np.asarray(im.convert("RGB"))[..., ::-1]
+            img = np.ascontiguousarray(img)
+            if cache is not None:
+                for k in [k for k in cache if k[0] == "img"]:
+                    del cache[k]
+                cache[("img", results["img_path"])] = img
         if self.to_float32:
             img = img.astype(np.float32)
         results["img"] = img
         results["img_shape"] = img.shape[:2]
         results["ori_shape"] = img.shape[:2]
+        return results
+
+    def plan(self, results):
+        if self.to_float32:
+            raise ValueError("LoadImageFromFile(to_float32=True) has no device form: vfm_augment_u8 reads the decoded uint8 image")
+        results = self(results)
+        results["aug_plan"] = dict(resize=None, crop=None, flip=0, wide=convert_is_wide())
         return results
 
 
@@ -101,6 +153,21 @@ class LoadAnnotations:
         self.reduce_zero_label = reduce_zero_label
 
     def __call__(self, results):
+        cache = results.get("_decoded")
+        seg = None if cache is None else cache.get(("seg", results["seg_map_path"]))
+        if seg is None:
+            seg = self._decode(results)
+            if cache is not None:
+                for k in [k for k in cache if k[0] == "seg"]:
+                    del cache[k]
+                cache[("seg", results["seg_map_path"])] = seg
+        results["gt_seg_map"] = seg
+        results.setdefault("seg_fields", []).append("gt_seg_map")
+        return results
+
+    plan = __call__
+
+    def _decode(self, results):
         from PIL import Image
         with Image.open(results["seg_map_path"]) as im:
             seg = np.asarray(im).astype(np.uint8)
@@ -118,9 +185,7 @@ class LoadAnnotations:
             cp = seg.copy()
             for old, new in lm.items():
                 seg[cp == old] = new
-        results["gt_seg_map"] = seg
-        results.setdefault("seg_fields", []).append("gt_seg_map")
-        return results
+        return seg
 
 
 @TRANSFORMS.register_module()
@@ -128,11 +193,12 @@ class Resize:
     """mmcv Resize: scale = (w, h); keep_ratio rescales so that the image fits inside the scale box (mmcv.rescale_size).
     Image bilinear, label maps nearest."""
 
+    STAGE = 1
+
     def __init__(self, scale=None, scale_factor=None, keep_ratio=False, **_):
         self.scale, self.scale_factor, self.keep_ratio = scale, scale_factor, keep_ratio
 
-    def __call__(self, results):
-        h, w = results["img"].shape[:2]
+    def _target(self, h, w):
         if self.scale is not None:
             sw, sh = self.scale
         else:
@@ -143,10 +209,27 @@ class Resize:
             nw, nh = int(w * float(k) + 0.5), int(h * float(k) + 0.5)
         else:
             nw, nh = int(sw), int(sh)
-        results["img"] = _resize(results["img"], (nh, nw), "bilinear")
+        return nh, nw
+
+    def _meta(self, results, h, w, nh, nw):
         results["img_shape"] = (nh, nw)
         results["scale_factor"] = (nw / w, nh / h)
         results["keep_ratio"] = self.keep_ratio
+
+    def plan(self, results):
+        h, w = results["img"].shape[:2]
+        nh, nw = self._target(h, w)
+        results["aug_plan"].update(resize=(nh, nw), scale_factor=(nw / w, nh / h), keep_ratio=self.keep_ratio)
+        self._meta(results, h, w, nh, nw)
+        if results.get("seg_fields"):    # the label is not resized as a whole: the crop gathers its window through these
+            results["_seg_idx"] = (nearest_index(h, nh), nearest_index(w, nw))
+        return results
+
+    def __call__(self, results):
+        h, w = results["img"].shape[:2]
+        nh, nw = self._target(h, w)
+        results["img"] = _resize(results["img"], (nh, nw), "bilinear")
+        self._meta(results, h, w, nh, nw)
         for key in results.get("seg_fields", []):
             results[key] = _resize(results[key], (nh, nw), "nearest")
         return results
@@ -157,26 +240,50 @@ class RandomCrop:
     """mmseg RandomCrop: a random crop_size window; with cat_max_ratio < 1 up to ten draws until no single category (ignore_index
     excluded) covers more than that share of the window and at least two categories are present."""
 
+    STAGE = 2
+
     def __init__(self, crop_size, cat_max_ratio=1.0, ignore_index=255):
         self.crop_size = (crop_size, crop_size) if isinstance(crop_size, int) else tuple(crop_size)
         self.cat_max_ratio, self.ignore_index = cat_max_ratio, ignore_index
 
-    def _bbox(self, img):
-        mh, mw = max(img.shape[0] - self.crop_size[0], 0), max(img.shape[1] - self.crop_size[1], 0)
+    def _bbox(self, shape):
+        mh, mw = max(shape[0] - self.crop_size[0], 0), max(shape[1] - self.crop_size[1], 0)
         oh, ow = np.random.randint(0, mh + 1), np.random.randint(0, mw + 1)
         return oh, oh + self.crop_size[0], ow, ow + self.crop_size[1]
 
-    def __call__(self, results):
-        img = results["img"]
-        box = self._bbox(img)
-        if self.cat_max_ratio < 1.0 and "gt_seg_map" in results:
+    def _draw(self, shape, window):
+        """The accepted box; window(box) is the label map inside a candidate box."""
+        box = self._bbox(shape)
+        if self.cat_max_ratio < 1.0 and window is not None:
             for _ in range(10):
-                seg = results["gt_seg_map"][box[0]:box[1], box[2]:box[3]]
-                labels, cnt = np.unique(seg, return_counts=True)
+                labels, cnt = np.unique(window(box), return_counts=True)
                 cnt = cnt[labels != self.ignore_index]
                 if len(cnt) > 1 and np.max(cnt) / np.sum(cnt) < self.cat_max_ratio:
                     break
-                box = self._bbox(img)
+                box = self._bbox(shape)
+        return box
+
+    def plan(self, results):
+        H, W = results["img_shape"]
+        idx = results.pop("_seg_idx", None)
+
+        def cut(seg, box):
+            if idx is None:
+                return seg[box[0]:box[1], box[2]:box[3]]
+            return seg[idx[0][box[0]:box[1]]][:, idx[1][box[2]:box[3]]]    # the resized label's window, gathered from the source label
+
+        box = self._draw((H, W), (lambda b: cut(results["gt_seg_map"], b)) if "gt_seg_map" in results else None)
+        y0, x0, y1, x1 = box[0], box[2], min(box[1], H), min(box[3], W)
+        results["aug_plan"]["crop"] = (int(y0), int(x0), int(y1 - y0), int(x1 - x0))
+        results["img_shape"] = (y1 - y0, x1 - x0)
+        for key in results.get("seg_fields", []):
+            results[key] = np.ascontiguousarray(cut(results[key], box))
+        return results
+
+    def __call__(self, results):
+        img = results["img"]
+        seg = results.get("gt_seg_map")
+        box = self._draw(img.shape, None if seg is None else (lambda b: seg[b[0]:b[1], b[2]:b[3]]))
         results["img"] = np.ascontiguousarray(img[box[0]:box[1], box[2]:box[3]])
         results["img_shape"] = results["img"].shape[:2]
         for key in results.get("seg_fields", []):
@@ -188,15 +295,33 @@ class RandomCrop:
 class RandomFlip:
     """mmcv RandomFlip (prob, direction='horizontal'): image and label maps flipped together."""
 
+    STAGE = 3
+
     def __init__(self, prob=None, direction="horizontal", **_):
         self.prob, self.direction = prob, direction
 
-    def __call__(self, results):
+    def _draw(self, results):
+        """The draw and the metainfo of both entries; returns the axis to flip, or None."""
         flip = self.prob is not None and np.random.rand() < self.prob
         results["flip"] = bool(flip)
         results["flip_direction"] = self.direction if flip else None
-        if flip:
-            ax = 1 if self.direction == "horizontal" else 0
+        if not flip:
+            return None
+        return 1 if self.direction == "horizontal" else 0
+
+    def plan(self, results):
+        ax = self._draw(results)
+        if ax is not None:
+            results["aug_plan"]["flip"] = 1 if ax == 1 else 2
+            idx = results.pop("_seg_idx", None)    # (no crop in this chain: the flip is of the whole resized label)
+            for key in results.get("seg_fields", []):
+                seg = results[key] if idx is None else results[key][idx[0]][:, idx[1]]
+                results[key] = np.ascontiguousarray(np.flip(seg, ax))
+        return results
+
+    def __call__(self, results):
+        ax = self._draw(results)
+        if ax is not None:
             results["img"] = np.ascontiguousarray(np.flip(results["img"], ax))
             for key in results.get("seg_fields", []):
                 results[key] = np.ascontiguousarray(np.flip(results[key], ax))
@@ -208,9 +333,26 @@ class PhotoMetricDistortion:
     """mmseg PhotoMetricDistortion on the BGR uint8 image: random brightness (+-32), contrast (x0.5..1.5, before or after the
     colour ops with equal chance), saturation (x0.5..1.5 in HSV) and hue (+-18 of 180), each applied with probability 1/2."""
 
+    STAGE = 4
+
     def __init__(self, brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18):
         self.bd, self.cl, self.cu = brightness_delta, contrast_range[0], contrast_range[1]
         self.sl, self.su, self.hd = saturation_range[0], saturation_range[1], hue_delta
+
+    def plan(self, results):
+        """The draws of __call__, in its order."""
+        p = results["aug_plan"]
+        p["brightness"] = (1, float(np.random.uniform(-self.bd, self.bd))) if np.random.randint(2) else (0, 0.0)
+        mode = np.random.randint(2)
+        p["mode"] = int(mode)
+        p["contrast"] = (0, 1.0)
+        if mode == 1 and np.random.randint(2):
+            p["contrast"] = (1, float(np.random.uniform(self.cl, self.cu)))
+        p["saturation"] = (1, float(np.random.uniform(self.sl, self.su))) if np.random.randint(2) else (0, 1.0)
+        p["hue"] = (1, int(np.random.randint(-self.hd, self.hd))) if np.random.randint(2) else (0, 0)
+        if mode == 0 and np.random.randint(2):
+            p["contrast"] = (2, float(np.random.uniform(self.cl, self.cu)))
+        return results
 
     @staticmethod
     def _convert(img, alpha=1.0, beta=0.0):
@@ -246,23 +388,61 @@ class PackSegInputs:
     def __init__(self, meta_keys=None):
         self.meta_keys = tuple(meta_keys) if meta_keys is not None else self.META
 
-    def __call__(self, results):
-        img = results["img"]
-        inputs = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1)))
+    def _pack(self, results, inputs, extra):
         gt = None
         if "gt_seg_map" in results:
             gt = torch.from_numpy(results["gt_seg_map"][None].astype(np.int64))
         meta = {k: results[k] for k in self.meta_keys if k in results}
+        meta.update(extra)
         return dict(inputs=inputs, data_samples=SegDataSample(gt_sem_seg=gt, metainfo=meta))
+
+    def plan(self, results):
+        """inputs: the decoded, untouched uint8 image, HWC and BGR - a view of the array the dataset's decode cache keeps, not a copy: read
+        it, do not write into it; metainfo: the host chain's, plus aug_plan."""
+        p = results["aug_plan"]
+        idx = results.pop("_seg_idx", None)    # a Resize with no crop after it (the label was loaded before it)
+        if idx is not None:
+            for key in results.get("seg_fields", []):
+                results[key] = np.ascontiguousarray(results[key][idx[0]][:, idx[1]])
+        if p["crop"] is None:
+            h, w = results["img_shape"]
+            p["crop"] = (0, 0, int(h), int(w))
+        return self._pack(results, torch.from_numpy(results["img"]), dict(aug_plan=p))
+
+    def __call__(self, results):
+        return self._pack(results, torch.from_numpy(np.ascontiguousarray(results["img"].transpose(2, 0, 1))), {})
 
 
 class Compose:
-    def __init__(self, pipeline):
+    """The transform chain.  device=True runs it in plan mode (the transforms' plan() entries): the sample then carries the decoded image
+    and metainfo["aug_plan"], and SegDataPreProcessor computes the chain on the GPU (ops.augment_u8).  A chain the device kernel cannot
+    express - a transform without a plan() entry, two resizes, a crop before the resize, ... - raises ValueError naming the transform."""
+
+    STAGES = {1: "Resize", 2: "RandomCrop", 3: "RandomFlip", 4: "PhotoMetricDistortion"}
+
+    def __init__(self, pipeline, device=False):
         self.transforms = [TRANSFORMS.build(t) if isinstance(t, dict) else t for t in (pipeline or [])]
+        self.device = bool(device)
+        if self.device:
+            stage = 0
+            for i, t in enumerate(self.transforms):
+                name = type(t).__name__
+                if not hasattr(t, "plan"):
+                    raise ValueError(f"device_augment: transform {name} has no device form")
+                if isinstance(t, LoadImageFromFile) and i != 0:
+                    raise ValueError(f"device_augment: {name} must open the chain")
+                s = getattr(t, "STAGE", None)
+                if s is not None:
+                    if s <= stage:
+                        raise ValueError(f"device_augment: {name} cannot follow {self.STAGES[stage]} (the device chain is Resize, RandomCrop, "
+                                         "RandomFlip, PhotoMetricDistortion, each at most once)")
+                    stage = s
+            if not self.transforms or not isinstance(self.transforms[0], LoadImageFromFile) or not isinstance(self.transforms[-1], PackSegInputs):
+                raise ValueError("device_augment: the chain must run from LoadImageFromFile to PackSegInputs")
 
     def __call__(self, results):
         for t in self.transforms:
-            results = t(results)
+            results = t.plan(results) if self.device else t(results)
             if results is None:
                 return None
         return results
@@ -277,12 +457,13 @@ class BaseSegDataset:
     METAINFO = dict(classes=(), palette=[])
 
     def __init__(self, data_root="", data_prefix=None, img_suffix=".jpg", seg_map_suffix=".png", pipeline=None, ignore_index=255,
-                 reduce_zero_label=False, test_mode=False, serialize_data=True, lazy_init=False, metainfo=None, **_):
+                 reduce_zero_label=False, test_mode=False, serialize_data=True, lazy_init=False, metainfo=None, device_augment=False, **_):
         self.data_root, self.ignore_index, self.reduce_zero_label, self.test_mode = data_root, ignore_index, reduce_zero_label, test_mode
         self.data_prefix = dict(data_prefix or dict(img_path="", seg_map_path=""))
         self.img_suffix, self.seg_map_suffix = img_suffix, seg_map_suffix
         self.metainfo = dict(self.METAINFO, **(metainfo or {}))
-        self.pipeline = Compose(pipeline)
+        self.pipeline = Compose(pipeline, device=device_augment)
+        self._decoded = {}    # plan mode: the last decoded image and label map by path (rare class sampling re-draws plans, not decodes)
         self.data_list = self.load_data_list()
 
     def load_data_list(self):
@@ -310,7 +491,14 @@ class BaseSegDataset:
         item = dict(self.data_list[idx])
         item["seg_fields"] = []
         item["sample_idx"] = idx
+        if self.pipeline.device:
+            item["_decoded"] = self._decoded
         return self.pipeline(item)
+
+    def set_device_augment(self, on):
+        """Switch the chain between the host form and plan mode (raises ValueError for a chain plan mode cannot express)."""
+        if bool(on) != self.pipeline.device:
+            self.pipeline = Compose(self.pipeline.transforms, device=on)
 
 
 @DATASETS.register_module()
@@ -365,6 +553,11 @@ class DGDataset:
                 assert len(self.samples_with_class[c]) > 0, f"no sample holds more than {self.rcs_min_pixels} pixels of class {c}"
             self.file_to_idx = {item["seg_map_path"].split("/")[-1]: i for i, item in enumerate(self.source.data_list)}
 
+    def set_device_augment(self, on):
+        for d in (self.source, getattr(self, "target", None)):
+            if d is not None:
+                set_device_augment(d, on)
+
     def get_rare_class_sample(self):
         c = np.random.choice(self.rcs_classes, p=self.rcs_classprob)
         f1 = np.random.choice(self.samples_with_class[c])
@@ -404,6 +597,16 @@ class UDADataset(DGDataset):
 
     def __len__(self):
         return len(self.source) * len(self.target)
+
+
+def set_device_augment(dataset, on):
+    """Plan mode on or off for a dataset and the datasets it wraps.  Asking it of a dataset that has no such switch is an error."""
+    fn = getattr(dataset, "set_device_augment", None)
+    if fn is not None:
+        fn(on)
+    elif on:
+        raise ValueError(f"device_augment: dataset {type(dataset).__name__} has no plan mode")
+    return dataset
 
 
 # ------------------------------------------------------------------------------------------------ sampling / loading
@@ -450,8 +653,10 @@ class DataLoaderIter:
     with rare class sampling the dataset ignores idx and draws class, file and crop from np.random, and equal worker seeds would make
     every rank train on the same samples."""
 
-    def __init__(self, dataset, batch_size=2, num_workers=0, shuffle=True, seed=0, rank=0, world=1, infinite=True):
+    def __init__(self, dataset, batch_size=2, num_workers=0, shuffle=True, seed=0, rank=0, world=1, infinite=True, device_augment=None):
         self.dataset = DATASETS.build(dataset) if isinstance(dataset, dict) else dataset
+        if device_augment is not None:     # (None: the dataset stays as it was built)
+            set_device_augment(self.dataset, device_augment)
         self.bs, self.i = batch_size, 0
         self.sampler = InfiniteSampler(len(self.dataset), shuffle, seed, rank, world) if infinite else range(rank, len(self.dataset), world)
         self.seed, self.rank, self.num_workers, self.epoch_offset = seed, rank, num_workers, 0

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvfmseg_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvfmseg_hip_f16.so")
 
 F32, BF16, U8, I64, SPLIT3 = 0, 1, 2, 3, 4
-ABI_VERSION = 7   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax: an older one lacks the symbols
+ABI_VERSION = 8   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax, 8 vfm_augment_u8: an older one lacks the symbols
 EP_NONE, EP_GELU, EP_RELU, EP_MUL_GELU_GRAD, EP_MUL, EP_QGELU, EP_MUL_QGELU_GRAD, EP_GELU_DGELU = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_QGELU = 0, 1, 2, 3
 
@@ -96,6 +96,13 @@ class SlideWin(C.Structure):
     _fields_ = [("crop", vp), ("nchw", ci), ("h", ci), ("w", ci), ("y0", ci), ("x0", ci), ("hc", ci), ("wc", ci)]
 
 
+class AugmentPlan(C.Structure):
+    """vfm_augment_plan (include/vfmseg_hip.h)."""
+    _fields_ = [("resize_h", ci), ("resize_w", ci), ("crop_y", ci), ("crop_x", ci), ("crop_h", ci), ("crop_w", ci), ("flip", ci), ("wide", ci),
+                ("brightness_on", ci), ("contrast_on", ci), ("saturation_on", ci), ("hue_on", ci), ("hue_delta", ci),
+                ("brightness_beta", C.c_double), ("contrast_alpha", C.c_double), ("saturation_alpha", C.c_double)]
+
+
 # name -> argtypes (return type is always int); mirrors include/vfmseg_hip.h
 SIGNATURES = {
     "vfm_cast": [vp, ci, cl, vp, ci, cl, cl, cl, vp, vp],
@@ -107,6 +114,7 @@ SIGNATURES = {
     "vfm_scale_by_device_scalar": [vp, vp, cl, vp],
     "vfm_colsum": [vp, ci, cl, cl, cl, vp, ci, vp, vp],
     "vfm_preprocess_u8": [vp, ci, ci, vp, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_float), ci, cf, vp],
+    "vfm_augment_u8": [vp, ci, ci, C.POINTER(AugmentPlan), vp, ci, ci, C.POINTER(C.c_float), C.POINTER(C.c_float), ci, cf, vp],
     "vfm_lora_pack": [vp, ci, cl, ci, vp],
     "vfm_slab_reduce": [vp, ci, cl, cl, cl, cf, vp, cl, cl, ci, vp],
     "vfm_dropout_mask": [vp, ci, cl, cf, u64, u64, vp],

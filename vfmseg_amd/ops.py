@@ -1239,6 +1239,29 @@ def preprocess_u8(img_u8, out, mean, std, bgr_to_rgb, pad_val=0.0):
     return out
 
 
+def augment_u8(img_u8, plan, out, mean, std, bgr_to_rgb, pad_val=0.0):
+    """img_u8 uint8 [Hs,Ws,3] as decoded (cuda, HWC) -> out fp32 [3,Hp,Wp]: the training chain Resize -> RandomCrop -> RandomFlip ->
+    PhotoMetricDistortion with the parameters of `plan` (datasets.Compose(device=True): metainfo["aug_plan"]), then channel swap,
+    normalise, pad - equal to preprocess_u8 of the host chain's crop (vfm_augment_u8, one launch)."""
+    lib = L.load()
+    assert img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3 and img_u8.is_contiguous()
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == 3
+    Hs, Ws, _ = img_u8.shape
+    _, Hp, Wp = out.shape
+    rs, (cy, cx, ch, cw) = plan.get("resize"), plan["crop"]
+    on_b, beta = plan.get("brightness", (0, 0.0))
+    pos_c, alpha_c = plan.get("contrast", (0, 1.0))
+    on_s, alpha_s = plan.get("saturation", (0, 1.0))
+    on_h, delta = plan.get("hue", (0, 0))
+    p = L.AugmentPlan(int(rs[0]) if rs else 0, int(rs[1]) if rs else 0, int(cy), int(cx), int(ch), int(cw), int(plan.get("flip", 0)),
+                      int(bool(plan.get("wide", False))), int(bool(on_b)), int(pos_c), int(bool(on_s)), int(bool(on_h)), int(delta),
+                      float(beta), float(alpha_c), float(alpha_s))
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    L.check(lib.vfm_augment_u8(L.ptr(img_u8), Hs, Ws, C.byref(p), L.ptr(out), Hp, Wp, m3, s3, int(bool(bgr_to_rgb)), float(pad_val), L.stream()),
+            "vfm_augment_u8")
+    return out
+
+
 def conf_gate_count(logits_nchw, window, thr, count):
     lib = L.load()
     B, Cc, H, W = logits_nchw.shape

@@ -133,9 +133,11 @@ class Runner:
         if ds is not None and not synthetic:
             # the reference's input pipeline (configs/dg/datasets/*.py -> DGDataset + rare class sampling over a CityscapesDataset
             # folder tree, mmseg transform chain, InfiniteSampler): vfmseg_amd.datasets.  Fails loudly when the data are not there.
-            from .datasets import DataLoaderIter
+            from .datasets import DataLoaderIter, device_augment_on
             shuffle = dict(dl.get("sampler", {}) or {}).get("shuffle", True)
-            loader = DataLoaderIter(ds, bs, dl.get("num_workers", 0), shuffle, seed, rank, world, infinite=True)
+            # train_dataloader.device_augment (VFMSEG_AUG_DEVICE overrides): the host draws, the GPU resizes, crops, flips and distorts
+            loader = DataLoaderIter(ds, bs, dl.get("num_workers", 0), shuffle, seed, rank, world, infinite=True,
+                                    device_augment=device_augment_on(dl))
         elif ds is not None and rank == 0:
             import warnings
             warnings.warn(f"train_dataloader.dataset ({ds.get('type', '?') if isinstance(ds, dict) else type(ds).__name__}) is NOT read: "
@@ -223,8 +225,9 @@ class Runner:
         metric = METRICS.build(dict(ev[0] if isinstance(ev, (list, tuple)) else ev))
         dl = dict(cfg.get("val_dataloader") or {})
         if not self.synthetic and dl.get("dataset") is not None:
-            from .datasets import DATASETS
+            from .datasets import DATASETS, device_augment_on, set_device_augment
             data = DATASETS.build(dl["dataset"]) if isinstance(dl["dataset"], dict) else dl["dataset"]
+            set_device_augment(data, device_augment_on(dl))
             if hasattr(data, "metainfo"):
                 metric.dataset_meta = dict(classes=data.metainfo["classes"])
         else:

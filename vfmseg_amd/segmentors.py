@@ -54,7 +54,8 @@ class SegDataPreProcessor(nn.Module):
     """mmseg SegDataPreProcessor (1.2.2 semantics, restated): decoded uint8 CHW images are channel-swapped (bgr_to_rgb),
     normalised and padded right/bottom to `size` with pad_val by one HIP kernel per sample (vfm_preprocess_u8), labels are
     padded with seg_pad_val, and img_shape / pad_shape / padding_size land in the sample's metainfo (stack_batch).
-    Float inputs are taken as already-normalised images (the synthetic benchmark path) and only stacked."""
+    Float inputs are taken as already-normalised images (the synthetic benchmark path) and only stacked.  A sample of the device pipeline
+    (metainfo["aug_plan"], datasets.Compose(device=True)) is a decoded uint8 HWC image: vfm_augment_u8 runs the training chain on it first."""
 
     def __init__(self, mean=None, std=None, size=None, size_divisor=None, pad_val=0, seg_pad_val=255, bgr_to_rgb=False,
                  rgb_to_bgr=False, batch_augments=None, test_cfg=None):
@@ -86,14 +87,21 @@ class SegDataPreProcessor(nn.Module):
             return dict(inputs=torch.stack(imgs, 0).cuda(non_blocking=True).contiguous(), data_samples=samples)
         if imgs[0].dtype != torch.uint8:
             raise TypeError(f"SegDataPreProcessor: expected uint8 or float32 images, got {imgs[0].dtype}")
-        hp, wp = self._target([tuple(i.shape[-2:]) for i in imgs], training)
+        # a sample of the device pipeline (datasets.Compose(device=True)) is the decoded HWC image plus metainfo["aug_plan"]: resize, crop,
+        # flip and photometric distortion run in the kernel that normalises and pads (ops.augment_u8); its shape is the plan's crop
+        plans = [None if samples is None else (getattr(samples[i], "metainfo", None) or {}).get("aug_plan") for i in range(len(imgs))]
+        shapes = [tuple(im.shape[-2:]) if p is None else tuple(p["crop"][2:]) for im, p in zip(imgs, plans)]
+        hp, wp = self._target(shapes, training)
         dev = torch.device("cuda", torch.cuda.current_device())
         out = torch.empty(len(imgs), 3, hp, wp, dtype=torch.float32, device=dev)
         for i, im in enumerate(imgs):
-            ops.preprocess_u8(im.to(dev, non_blocking=True).contiguous(), out[i], self.mean_l, self.std_l, self.channel_swap, self.pad_val)
+            if plans[i] is None:
+                ops.preprocess_u8(im.to(dev, non_blocking=True).contiguous(), out[i], self.mean_l, self.std_l, self.channel_swap, self.pad_val)
+            else:
+                ops.augment_u8(im.to(dev, non_blocking=True).contiguous(), plans[i], out[i], self.mean_l, self.std_l, self.channel_swap, self.pad_val)
             if samples is not None:
                 s_ = samples[i]
-                h, w = im.shape[-2:]
+                h, w = shapes[i]
                 gt = getattr(s_, "gt_sem_seg", None)
                 g = None if gt is None else (gt if torch.is_tensor(gt) else gt.data)
                 if training and g is not None and tuple(g.shape[-2:]) != (hp, wp):   # (test mode: stack_batch pads the images only)
@@ -101,6 +109,7 @@ class SegDataPreProcessor(nn.Module):
                     pad[..., :g.shape[-2], :g.shape[-1]] = g
                     s_.gt_sem_seg = PixelData(pad)
                 meta = dict(getattr(s_, "metainfo", {}) or {})
+                meta.pop("aug_plan", None)    # consumed: what is left is the host chain's metainfo
                 meta.update(img_shape=(hp, wp), pad_shape=(hp, wp), padding_size=(0, wp - w, 0, hp - h))
                 meta.setdefault("ori_shape", (h, w))
                 s_.metainfo = meta
