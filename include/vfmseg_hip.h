@@ -376,6 +376,30 @@ int vfm_class_presence(const int64_t* label, int B, long n, uint32_t* bits, void
 int vfm_class_mix(const float* src_img, const float* tgt_img, const int64_t* src_label, const int64_t* pseudo_label,
                   const uint32_t* chosen, const int32_t* count, long total, int ignore_top, int ignore_bottom, int B, int H, int W,
                   float* mixed_img, int64_t* mixed_label, float* mix_weight, uint8_t* mask, void* stream);
+/* ---- loss options of the fused cross-entropy as weight maps (ABI 9; csrc/ohem.hip, csrc/ohem_select.h; fp32 / int64 / int32 in both builds) ----
+ * mmseg 1.2.2 OHEMPixelSampler (thresh branch), CrossEntropyLoss(class_weight=, avg_non_ignore=).  Every option becomes a per-pixel fp32
+ * weight map [B,H,W] for vfm_upsample_ce_w plus one device scalar that rescales its loss and gradient.  Nothing is read on the host.
+ * vfm_ohem_prob: p fp32 [B,H,W] = softmax(bilinear_up(logits_low))[label] in the arithmetic of vfm_upsample_ce (ignored pixels: -1, which the
+ *   selection skips); state int32 [VFM_OHEM_STATE_INTS], ZEROED by the caller, receives n = #valid, #(p < thresh) and the first histogram.
+ * vfm_ohem_threshold: t = max(s[k], thresh), s = the valid p sorted ascending, k = min(k_request, n - 1); t = thresh when n == 0.  Exact:
+ *   three rounds of integer histograms over the 31 key bits.  Afterwards state[VFM_OHEM_T] holds the bits of t, state[VFM_OHEM_K] = k.
+ * vfm_label_weight: weight[i] = [label valid] * [p[i] < t] * class_weight[label[i]] * pix_weight[i]; p+state (t is read from state),
+ *   class_weight fp32 [C] and pix_weight fp32 [B,H,W] are each optional (NULL = factor 1).  counts int32 [VFM_LABEL_COUNT_INTS], zeroed by the
+ *   caller, receives the number of valid pixels per class (last entry: valid labels outside [0,C), weight 0 under class weights) and
+ *   norm fp32 [2] = (B*H*W / (avg_factor + 2^-23), avg_factor) with avg_factor = sum_c class_weight[c] * counts[c] (class weights given),
+ *   else the number of valid pixels (avg_non_ignore != 0), else B*H*W; counts and norm may both be NULL, weight may be NULL when only
+ *   the normaliser is wanted. */
+#define VFM_OHEM_STATE_INTS 3080
+#define VFM_OHEM_N 0
+#define VFM_OHEM_NLT 1
+#define VFM_OHEM_K 2
+#define VFM_OHEM_T 6
+#define VFM_LABEL_COUNT_INTS 33
+int vfm_ohem_prob(const float* logits_low, const int64_t* label, int B, int h, int w, int C, int H, int W, int ignore_index,
+                  float thresh, float* p, int32_t* state, void* stream);
+int vfm_ohem_threshold(const float* p, long n_pix, long k_request, float thresh, int32_t* state, void* stream);
+int vfm_label_weight(const int64_t* label, const float* p, const int32_t* state, const float* class_weight, const float* pix_weight,
+                     int C, long n_pix, int ignore_index, int avg_non_ignore, float* weight, int32_t* counts, float* norm, void* stream);
 /* After vfm_upsample_ce: loss[0] = scale * sum(loss_parts[0..n)), acc[0] = 100 * counts[0] / (counts[1] + eps) (mmseg `accuracy`
  * over the valid pixels, linear_head.py:95-108), then counts is reset to (0, 0) for the next call. */
 int vfm_ce_finish(const float* loss_parts, long n, float scale, int32_t* counts, float eps, float* loss, float* acc, void* stream);

@@ -127,8 +127,10 @@ class _PackCache:
         import weakref
         key = (tuple((w.data_ptr(), tuple(w.shape)) for w in weights), tuple(layouts), Kp, cd)
         e = self.entries.get(key)
-        if e is not None and any(r() is None for r in e["refs"]):
-            e = None   # the storage address was recycled by other tensors
+        if e is not None and any(r() is not w for r, w in zip(e["refs"], weights)):
+            # the storage address was recycled by other tensors: the entry's parameters died, or they live on in other storage (module.to(),
+            # an optimiser that moves them into its flat buffer) - alive weak references alone would let their stale image answer
+            e = None
         stamp = self._stamp(weights)
         if e is None:
             N = sum(d[0] for d in dims)
@@ -149,12 +151,14 @@ class _PackCache:
         return e["wp"]
 
     def refresh_all(self):
-        live = {}
+        # strong references for the length of this call: the garbage collector may run at any allocation below and take a dead model's
+        # parameters (and with them the weak references) between the pruning pass and the passes that read them
+        live, held = {}, {}
         for key, e in self.entries.items():
             ws = [r() for r in e["refs"]]
             if any(w is None for w in ws) or tuple((w.data_ptr(), tuple(w.shape)) for w in ws) != key[0]:
                 continue
-            live[key] = e
+            live[key], held[key] = e, ws
         if len(live) != len(self.entries):
             self.entries, self.table = live, None
         sig = tuple(self.entries.keys())
@@ -162,8 +166,8 @@ class _PackCache:
             jobs = []
             for key, e in self.entries.items():
                 r0 = 0
-                for r, l, d in zip(e["refs"], e["layouts"], e["dims"]):
-                    w = r().detach()
+                for w, l, d in zip(held[key], e["layouts"], e["dims"]):
+                    w = w.detach()
                     src = w if w.dtype == torch.float32 and w.is_contiguous() else None
                     if src is None:
                         jobs = None
@@ -179,11 +183,11 @@ class _PackCache:
         else:   # a non-fp32 / non-contiguous parameter: pack one by one
             for key, e in self.entries.items():
                 r0 = 0
-                for r, l, d in zip(e["refs"], e["layouts"], e["dims"]):
-                    _pack(r().detach(), l, e["wp"][r0:r0 + d[0]])
+                for w, l, d in zip(held[key], e["layouts"], e["dims"]):
+                    _pack(w.detach(), l, e["wp"][r0:r0 + d[0]])
                     r0 += d[0]
         for key, e in self.entries.items():
-            e["stamp"] = self._stamp([r() for r in e["refs"]])
+            e["stamp"] = self._stamp(held[key])
             # the re-pack rewrote wp behind torch's version counter: a split-bf16 image cached on it (ops.split3) is stale
             if hasattr(e["wp"], "_vfm_split3"):
                 del e["wp"]._vfm_split3
@@ -893,6 +897,32 @@ class UpsampleCEWeightedFn(torch.autograd.Function):
         if ctx.lw != 1.0:
             ops.axpby(g, ctx.lw, g, 0.0)
         return g, None, None, None, None
+
+
+class UpsampleCENormFn(torch.autograd.Function):
+    """UpsampleCEWeightedFn whose loss and gradient are multiplied by a device scalar norm[0] = B*H*W / (avg_factor + eps) (ops.label_weight):
+    loss = loss_weight * sum_valid(w * -log p[label]) / (avg_factor + eps), the form of mmseg's CrossEntropyLoss with class weights,
+    avg_non_ignore and a pixel sampler.  weight may be None (all ones); the weights and norm are constants."""
+
+    @staticmethod
+    def forward(ctx, logits_low, label, weight, norm, ignore_index, loss_weight):
+        loss, acc, dl = ops.upsample_ce_w_loss_acc(logits_low.contiguous(), label, weight, ignore_index, need_grad=True)
+        ops.scale_by_device_scalar(loss, norm)   # (a one-element view of the kernel's (loss, acc) pair: the accuracy stays)
+        ops.scale_by_device_scalar(dl, norm)
+        ctx.save_for_backward(dl)
+        ctx.lw = loss_weight
+        ctx.mark_non_differentiable(acc)
+        if loss_weight != 1.0:
+            ops.axpby(loss, loss_weight, loss, 0.0)
+        return loss.view(()), acc
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (g,) = ctx.saved_tensors
+        ops.scale_by_device_scalar(g, dloss.contiguous().view(1))
+        if ctx.lw != 1.0:
+            ops.axpby(g, ctx.lw, g, 0.0)
+        return g, None, None, None, None, None
 
 
 class UpsampleCEAllFn(torch.autograd.Function):

@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import functional as Fh
 from . import ops
+from .loss_options import loss_with_options
 from .precision import compute_dtype, is_half
 from .registry import MODELS
 
@@ -46,30 +47,59 @@ def as_featpack(inputs, in_index=(0, 1, 2, 3)):
 
 @MODELS.register_module()
 class CrossEntropyLoss(nn.Module):
-    """mmseg CrossEntropyLoss(use_sigmoid=False, avg_non_ignore=False): mean over ALL pixels, ignored ones add 0."""
+    """mmseg CrossEntropyLoss(use_sigmoid=False, reduction='mean').  Without options: the mean over ALL pixels, ignored ones add 0.
+    class_weight (a list of num_classes floats) weighs every pixel by its label's class and averages over the sum of those weights;
+    avg_non_ignore=True averages over the valid pixels (loss_options.py)."""
 
     def __init__(self, use_sigmoid=False, loss_weight=1.0, loss_name="loss_ce", reduction="mean", class_weight=None,
                  avg_non_ignore=False, **kw):
         super().__init__()
-        if use_sigmoid or class_weight is not None or avg_non_ignore or reduction != "mean":
-            raise NotImplementedError("HIP path implements the reference configs' softmax CE (mean over all pixels)")
+        if use_sigmoid or reduction != "mean":
+            raise NotImplementedError("HIP path implements the reference configs' softmax CE (reduction='mean')")
+        if isinstance(class_weight, str):
+            raise NotImplementedError(f"CrossEntropyLoss: class_weight={class_weight!r}: class weights from a file are not read; pass the list of floats")
+        self.class_weight = None if class_weight is None else [float(v) for v in class_weight]
+        self.avg_non_ignore = bool(avg_non_ignore)
         self.loss_weight, self._loss_name = loss_weight, loss_name
+        self._cw = {}
 
     @property
     def loss_name(self):
         return self._loss_name
 
+    @property
+    def has_options(self):
+        return self.class_weight is not None or self.avg_non_ignore
+
+    def class_weight_on(self, device, num_classes):
+        """The class weights as fp32 [num_classes] on `device` (copied once), or None."""
+        if self.class_weight is None:
+            return None
+        if len(self.class_weight) != num_classes:
+            raise ValueError(f"CrossEntropyLoss: class_weight has {len(self.class_weight)} entries for {num_classes} classes")
+        key = str(device)
+        if key not in self._cw:
+            self._cw[key] = torch.tensor(self.class_weight, dtype=torch.float32).to(device)
+        return self._cw[key]
+
     def forward(self, cls_score, label, weight=None, ignore_index=255, **kw):
         """cls_score NCHW fp32 at label resolution (API parity); the heads use the fused low-res path instead.  weight: per-pixel
-        fp32 [B,H,W] (mmseg's `weight=seg_weight`: the loss term of every pixel is multiplied before the all-pixel mean) or None."""
+        fp32 [B,H,W] (mmseg's `weight=seg_weight`: the loss term of every pixel is multiplied before the mean; it does not enter avg_factor) or None."""
         lg = torch.empty(cls_score.shape[0], cls_score.shape[2], cls_score.shape[3], cls_score.shape[1],
                          dtype=torch.float32, device=cls_score.device)
         ops.permute_copy(cls_score.detach(), (0, 2, 3, 1), lg)
-        if weight is not None:
-            loss, _ = Fh.UpsampleCEWeightedFn.apply(lg, label.contiguous(), weight.float().contiguous(), ignore_index, self.loss_weight)
-        else:
-            loss, _ = Fh.UpsampleCEFn.apply(lg, label.contiguous(), ignore_index, self.loss_weight)
+        loss, _ = loss_with_options(lg, label.contiguous(), ignore_index, self.loss_weight, None, self.class_weight_on(lg.device, lg.shape[-1]),
+                                    self.avg_non_ignore, weight)
         return loss
+
+
+def loss_options_named(head_cfg):
+    """The loss options a decode head's config turns on, by name: 'sampler', 'class_weight', 'avg_non_ignore'."""
+    named = ["sampler"] if head_cfg.get("sampler") is not None else []
+    ld = head_cfg.get("loss_decode") or {}
+    if isinstance(ld, dict):
+        named += [k for k in ("class_weight", "avg_non_ignore") if ld.get(k)]
+    return named
 
 
 class BaseDecodeHead(nn.Module):
@@ -89,7 +119,7 @@ class BaseDecodeHead(nn.Module):
         if align_corners:
             raise NotImplementedError("align_corners=True is not on the HIP path (all reference configs use False)")
         self.loss_decode = MODELS.build(loss_decode)
-        self.sampler = None
+        self.sampler = MODELS.build(sampler, context=self) if sampler is not None else None
         self.conv_seg = nn.Conv2d(channels, self.out_channels, kernel_size=1)
         nn.init.normal_(self.conv_seg.weight, std=0.01)
         nn.init.zeros_(self.conv_seg.bias)
@@ -97,11 +127,19 @@ class BaseDecodeHead(nn.Module):
     def _stack_batch_gt(self, batch_data_samples):
         return torch.stack([d.gt_sem_seg.data for d in batch_data_samples], dim=0)
 
+    def _ce(self, logits_nhwc, label, seg_weight=None):
+        """(loss, acc_seg) under the head's sampler and the loss module's options; without any, exactly the calls made before they existed."""
+        ld = self.loss_decode
+        if self.sampler is not None and seg_weight is not None:
+            raise ValueError("loss_by_feat: seg_weight and sampler= would both set the pixel weights; give one of them")
+        return loss_with_options(logits_nhwc, label, self.ignore_index, ld.loss_weight, self.sampler,
+                                 ld.class_weight_on(logits_nhwc.device, logits_nhwc.shape[-1]), ld.avg_non_ignore, seg_weight)
+
     # ---- shared loss path (linear_head.py:72-113 / VFMHead.py:91-133)
     def _loss_from_lowres(self, logits_nhwc, seg_label, return_logits):
         label = seg_label.squeeze(1).contiguous()
         # loss and accuracy (mmseg `accuracy`: 100 * correct / (valid + eps)) come out of the fused kernel pair
-        loss, acc = Fh.UpsampleCEFn.apply(logits_nhwc, label, self.ignore_index, self.loss_decode.loss_weight)
+        loss, acc = self._ce(logits_nhwc, label)
         losses = {self.loss_decode.loss_name: loss, "acc_seg": acc}
         if return_logits:
             B, h, w, C = logits_nhwc.shape
@@ -115,11 +153,7 @@ class BaseDecodeHead(nn.Module):
         """mmseg BaseDecodeHead.loss_by_feat on the low-resolution NHWC logits: {loss_name, acc_seg}.  seg_weight fp32 [B,H,W] weighs every
         pixel's loss term (DACS's mix_weight); the accuracy is unweighted."""
         label = (seg_label.squeeze(1) if seg_label.dim() == 4 else seg_label).contiguous()
-        if seg_weight is None:
-            loss, acc = Fh.UpsampleCEFn.apply(seg_logits_nhwc, label, self.ignore_index, self.loss_decode.loss_weight)
-        else:
-            loss, acc = Fh.UpsampleCEWeightedFn.apply(seg_logits_nhwc, label, seg_weight.contiguous(), self.ignore_index,
-                                                      self.loss_decode.loss_weight)
+        loss, acc = self._ce(seg_logits_nhwc, label, seg_weight)
         return {self.loss_decode.loss_name: loss, "acc_seg": acc}
 
     def predict_by_feat(self, seg_logits_nhwc, batch_img_metas):
@@ -544,6 +578,11 @@ class HRDAHead(BaseDecodeHead):
             raise NotImplementedError("HRDAHead: only seg_head=LinearHead with single_scale_head=AttentionHead (DAFormer / ASPP heads are not on the HIP path)")
         if lr_loss_weight > 0:
             raise NotImplementedError("HRDAHead: lr_loss_weight > 0 is not used by the reference config and not implemented")
+        for where, cfg in (("HRDAHead", kwargs), ("seg_head", seg_head), ("single_scale_head", single_scale_head)):
+            named = loss_options_named(cfg)
+            if named:
+                raise NotImplementedError(f"HRDAHead: {', '.join(named)} (set on {where}) would be ignored by the HRDA loss path "
+                                          "(UpsampleCEAllFn: plain cross-entropy on the fused and the detail logits); remove the option")
         super().__init__(in_channels=seg_head["in_channels"][0], channels=seg_head["channels"], num_classes=seg_head["num_classes"])
         self.os = 4
         self.head = MODELS.build(seg_head)

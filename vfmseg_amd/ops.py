@@ -1122,6 +1122,64 @@ def upsample_ce_w_loss_acc(logits_low, label, weight=None, ignore_index=255, nee
     return out[0:1], out[1:2], dl
 
 
+OHEM_STATE_INTS, OHEM_N, OHEM_NLT, OHEM_K, OHEM_T, LABEL_COUNT_INTS = 3080, 0, 1, 2, 6, 33   # include/vfmseg_hip.h VFM_OHEM_* / VFM_LABEL_COUNT_INTS
+
+
+def ohem_prob(logits_low, label, thresh, ignore_index=255):
+    """p fp32 [B,H,W] = softmax(bilinear_up(logits_low))[label] (ignored pixels: -1) and the zero-initialised selection state int32
+    [OHEM_STATE_INTS] with n = state[OHEM_N], #(p < thresh) = state[OHEM_NLT] and the first histogram (vfm_ohem_prob)."""
+    lib = L.load()
+    B, h, w, Cc = logits_low.shape
+    _, H, W = label.shape
+    assert logits_low.dtype == torch.float32 and logits_low.is_contiguous() and label.dtype == torch.int64 and label.is_contiguous()
+    dev = logits_low.device
+    p = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    state = torch.zeros(OHEM_STATE_INTS, dtype=torch.int32, device=dev)
+    L.check(lib.vfm_ohem_prob(L.ptr(logits_low), L.ptr(label), B, h, w, Cc, H, W, int(ignore_index), float(thresh), L.ptr(p), L.ptr(state),
+                              L.stream()), "vfm_ohem_prob")
+    return p, state
+
+
+def ohem_threshold(p, state, k_request, thresh):
+    """After ohem_prob: the device float t = max(k-th smallest valid p, thresh), k = min(k_request, n - 1), as a view of `state`
+    (vfm_ohem_threshold; exact, no host read)."""
+    lib = L.load()
+    assert p.dtype == torch.float32 and p.is_contiguous() and state.dtype == torch.int32 and state.numel() == OHEM_STATE_INTS
+    L.check(lib.vfm_ohem_threshold(L.ptr(p), p.numel(), int(k_request), float(thresh), L.ptr(state), L.stream()), "vfm_ohem_threshold")
+    return state[OHEM_T:OHEM_T + 1].view(torch.float32)
+
+
+def label_weight(label, num_classes, p=None, state=None, class_weight=None, pix_weight=None, ignore_index=255, avg_non_ignore=False,
+                 want_weight=True, want_norm=True):
+    """(weight fp32 [B,H,W] or None, norm fp32 [2] or None, counts int32 [LABEL_COUNT_INTS] or None) of vfm_label_weight:
+    weight = [valid] * [p < t] * class_weight[label] * pix_weight, norm = (B*H*W / (avg_factor + 2^-23), avg_factor)."""
+    lib = L.load()
+    assert label.dtype == torch.int64 and label.is_contiguous()
+    dev = label.device
+    for t_ in (p, pix_weight):
+        assert t_ is None or (t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == label.numel())
+    assert class_weight is None or (class_weight.dtype == torch.float32 and class_weight.is_contiguous() and class_weight.numel() == num_classes)
+    assert (p is None) == (state is None)
+    weight = torch.empty(label.shape, dtype=torch.float32, device=dev) if want_weight else None
+    counts = torch.zeros(LABEL_COUNT_INTS, dtype=torch.int32, device=dev) if want_norm else None
+    norm = torch.empty(2, dtype=torch.float32, device=dev) if want_norm else None
+    L.check(lib.vfm_label_weight(L.ptr(label), L.ptr(p), L.ptr(state), L.ptr(class_weight), L.ptr(pix_weight), int(num_classes), label.numel(),
+                                 int(ignore_index), int(bool(avg_non_ignore)), L.ptr(weight), L.ptr(counts), L.ptr(norm), L.stream()),
+            "vfm_label_weight")
+    return weight, norm, counts
+
+
+def ohem_weight(logits_low, label, thresh, k_request, ignore_index=255, class_weight=None, pix_weight=None, avg_non_ignore=False,
+                want_norm=False):
+    """The OHEM chain in one call: ohem_prob -> ohem_threshold -> label_weight.  Returns (weight, p, t, state, norm, counts); t is a device
+    float [1], state the counters (n, #(p < thresh), k at OHEM_N / OHEM_NLT / OHEM_K)."""
+    p, state = ohem_prob(logits_low, label, thresh, ignore_index)
+    t = ohem_threshold(p, state, k_request, thresh)
+    weight, norm, counts = label_weight(label, logits_low.shape[-1], p, state, class_weight, pix_weight, ignore_index, avg_non_ignore,
+                                        want_weight=True, want_norm=want_norm)
+    return weight, p, t, state, norm, counts
+
+
 def pseudo_label(logits_low, size, thr, count, want_prob=False):
     """Teacher logits fp32 NHWC [B,h,w,C] -> (pseudo_label int64 [B,H,W], pseudo_prob fp32 [B,H,W] or None) at size = (H, W): bilinear
     (align_corners=False) + softmax + torch.max in registers; count (int32 [1], device) += #pixels with max prob >= thr."""

@@ -57,6 +57,9 @@ class DACS(EncoderDecoder):
         if head_type not in _HEADS:
             raise NotImplementedError(f"DACS: decode_head type {head_type!r}: the self-training loop runs with {' / '.join(_HEADS)} "
                                       "(HRDAHead and Mask2Former heads are not on this path)")
+        if dict(cfg["decode_head"]).get("sampler") is not None:
+            raise NotImplementedError("DACS: decode_head sampler=: the mixed-image loss passes seg_weight (the pseudo-label weight), and a pixel "
+                                      "sampler would set the same weights (mmseg lets the sampler overwrite them); remove the sampler")
         super().__init__(backbone=cfg["backbone"], decode_head=cfg["decode_head"], train_cfg=cfg.get("train_cfg"),
                          test_cfg=cfg.get("test_cfg"), data_preprocessor=cfg.get("data_preprocessor"))
         self.local_iter = 0   # a plain attribute, as in the reference: a resumed run starts at 0 and re-initialises the teacher from the student
