@@ -513,6 +513,28 @@ int vfm_adamw_guarded(float* p, float* g, float* m, float* v, long n, const long
                       int zero_grad, int vec4, const int* skip, const float* amp_state, void* stream);
 int vfm_amp_update(const int* flag, float* amp_state, float growth, float backoff, int interval, int dynamic, void* stream);
 
+/* ---- gradient clipping on the device (ABI 10; csrc/gradnorm.hip; mmengine OptimWrapper clip_grad -> torch.nn.utils.clip_grad_norm_ /
+ * clip_grad_value_; fp32 only, the same in both builds) ----
+ * vfm_grad_norm : the norm (norm_kind: 2-norm, 1-norm or max |g|) of the flat gradient buffer g[n] AS THE OPTIMISER WILL SEE IT, i.e. of
+ *   s * g with s = pre_scale (the data-parallel 1/world) or, with amp_state (float[4] as above), pre_scale / amp_state[0] - and torch's
+ *   clip coefficient, both left on the device:  clip_state = float[4] { total norm, min(1, max_norm / (total + 1e-6)), 0, 0 }.
+ *   nonfinite (int32[1], may be NULL) is set to 1 when any element of g is an inf or a NaN and to 0 otherwise; the total norm is then
+ *   non-finite.  n == 0: norm 0, coefficient 1.  workspace: VFM_GRAD_NORM_WS_DOUBLES doubles, 8-byte aligned, contents irrelevant on
+ *   entry.  g needs float alignment only (float4 loads when it is 16-byte aligned).  Two launches, a grid that depends on n alone, every
+ *   sum in a fixed order (per-thread fp32 chains of at most 4 ceil(n / 2^21) + 1 terms, everything across threads in double), no float
+ *   atomics: the same buffer gives the same bits on every call.
+ * vfm_adamw_clip : vfm_adamw_guarded that consumes the clipping on the device.  clip_coef (device, may be NULL): the gradients are
+ *   multiplied by *clip_coef on top of grad_scale (&clip_state[1]).  clip_value > 0: the un-scaled gradient grad_scale * g is clamped to
+ *   [-clip_value, clip_value] before the moments (clip_grad_value_); <= 0: off.  NULL and 0 are vfm_adamw_guarded, bit for bit. */
+enum { VFM_NORM_INF = 0, VFM_NORM_L1 = 1, VFM_NORM_L2 = 2 };
+enum { VFM_GRAD_NORM_WS_DOUBLES = 4096 };
+int vfm_grad_norm(const float* g, long n, int norm_kind, float max_norm, float pre_scale, const float* amp_state, double* workspace,
+                  float* clip_state, int* nonfinite, void* stream);
+int vfm_adamw_clip(float* p, float* g, float* m, float* v, long n, const long* seg_start, const float* seg_lr_mult,
+                   const float* seg_wd, int n_seg, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                   int zero_grad, int vec4, const int* skip, const float* amp_state, const float* clip_coef, float clip_value,
+                   void* stream);
+
 /* ---- launch plans -------------------------------------------------------------------------------------- */
 /* A recorded sequence of the calls above, replayed in order on one stream by ONE call.  The hot path's backbone is a fixed launch
  * sequence per step (18 launches per transformer block: rein/models/backbones/dino_v2.py:259-291 forward_features and its backward) over

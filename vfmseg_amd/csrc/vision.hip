@@ -1063,12 +1063,16 @@ extern "C" int vfm_slide_finalize(float* preds, const float* count, uint8_t* arg
 // float4 per lane (every segment starts on a 16-float boundary of the flat buffers when seg_start % 4 == 0: a vector never
 // straddles two parameter groups), the segment table searched in LDS once per vector; 28 B/param of traffic (+4 B when the
 // gradient is cleared in the same pass: zero_grad fused, no separate 66 MB fill launch).
-template <bool VEC>
+// CLAMP (clip_grad_value_): the un-scaled gradient is clamped to [-clip_value, clip_value] before the moments; a template parameter, so
+// that the un-clamped instantiation is the kernel it was.  clip_coef (device, may be NULL): torch's clip_grad_norm_ coefficient as
+// vfm_grad_norm left it (gradnorm.hip), folded into the gradient scale - multiplying by a coefficient of exactly 1 changes no bit.
+template <bool VEC, bool CLAMP>
 __global__ void __launch_bounds__(256) k_adamw(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                                                const long* __restrict__ seg_start, const float* __restrict__ seg_lr,
                                                const float* __restrict__ seg_wd, int n_seg, float lr, float b1, float b2, float eps, float bc1,
                                                float bc2_sqrt, float gscale, int zero_grad, const int* __restrict__ skip,
-                                               const float* __restrict__ amp_state) {
+                                               const float* __restrict__ amp_state, const float* __restrict__ clip_coef,
+                                               float clip_value) {
   extern __shared__ long s_start[];
   // amp_state (device, AmpOptimWrapper): [0] loss scale, [2] optimiser steps taken so far.  With it the un-scale factor and the bias
   // corrections are formed here, so neither the scale nor the step count has to be known on the host when the launch is enqueued.
@@ -1078,6 +1082,7 @@ __global__ void __launch_bounds__(256) k_adamw(float* __restrict__ p, float* __r
     bc1 = 1.f - powf(b1, st);
     bc2_sqrt = sqrtf(1.f - powf(b2, st));
   }
+  if (clip_coef != nullptr) gscale = gscale * clip_coef[0];
   // loss-scaled training (AmpOptimWrapper): a step whose gradients hold an inf / NaN leaves parameters and moments alone.  The flag is
   // read on the device, so the host does not have to wait for the backward pass before it can enqueue this launch.
   const bool skipped = skip != nullptr && *skip != 0;
@@ -1111,7 +1116,8 @@ __global__ void __launch_bounds__(256) k_adamw(float* __restrict__ p, float* __r
     }
 #pragma unroll
     for (int k = 0; k < W; ++k) {
-      const float gi = gg[k] * gscale;
+      float gi = gg[k] * gscale;
+      if constexpr (CLAMP) gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // (a NaN stays one, as in torch)
       const float mi = b1 * mm[k] + (1.f - b1) * gi;
       const float vi = b2 * vv[k] + (1.f - b2) * gi * gi;
       const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -1132,8 +1138,8 @@ __global__ void __launch_bounds__(256) k_adamw(float* __restrict__ p, float* __r
 extern "C" int vfm_adamw(float* p, float* g, float* m, float* v, long n, const long* seg_start, const float* seg_lr_mult,
                          const float* seg_wd, int n_seg, float lr, float beta1, float beta2, float eps, int step,
                          float grad_scale, int zero_grad, int vec4, void* stream) {
-  return vfm_adamw_guarded(p, g, m, v, n, seg_start, seg_lr_mult, seg_wd, n_seg, lr, beta1, beta2, eps, step, grad_scale, zero_grad, vec4, nullptr, nullptr,
-                           stream);
+  return vfm_adamw_clip(p, g, m, v, n, seg_start, seg_lr_mult, seg_wd, n_seg, lr, beta1, beta2, eps, step, grad_scale, zero_grad, vec4, nullptr, nullptr,
+                        nullptr, 0.f, stream);
 }
 // one thread: torch GradScaler.update() + the optimiser's step count, on the device
 __global__ void k_amp_update(const int* __restrict__ flag, float* __restrict__ st, float growth, float backoff, int interval, int dynamic) {
@@ -1157,21 +1163,35 @@ extern "C" int vfm_amp_update(const int* flag, float* amp_state, float growth, f
 extern "C" int vfm_adamw_guarded(float* p, float* g, float* m, float* v, long n, const long* seg_start, const float* seg_lr_mult,
                                  const float* seg_wd, int n_seg, float lr, float beta1, float beta2, float eps, int step,
                                  float grad_scale, int zero_grad, int vec4, const int* skip, const float* amp_state, void* stream) {
+  return vfm_adamw_clip(p, g, m, v, n, seg_start, seg_lr_mult, seg_wd, n_seg, lr, beta1, beta2, eps, step, grad_scale, zero_grad, vec4, skip, amp_state,
+                        nullptr, 0.f, stream);
+}
+template <bool VEC, bool CLAMP, typename... A>
+static void adamw_launch(int grid, size_t lds, hipStream_t st, A... a) {
+  hipLaunchKernelGGL((k_adamw<VEC, CLAMP>), dim3(grid), dim3(256), lds, st, a...);
+}
+extern "C" int vfm_adamw_clip(float* p, float* g, float* m, float* v, long n, const long* seg_start, const float* seg_lr_mult,
+                              const float* seg_wd, int n_seg, float lr, float beta1, float beta2, float eps, int step,
+                              float grad_scale, int zero_grad, int vec4, const int* skip, const float* amp_state,
+                              const float* clip_coef, float clip_value, void* stream) {
   VFM_CHECK(n_seg >= 1 && n_seg <= 8192 && step >= 1, VFM_E_INVAL, "vfm_adamw: n_seg/step");
+  VFM_CHECK(clip_value == clip_value, VFM_E_INVAL, "vfm_adamw_clip: clip_value is a NaN");
   if (n == 0) return VFM_OK;
   const float bc1 = 1.f - powf(beta1, (float)step);
   const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
   auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   const bool vec = vec4 && n % 4 == 0 && a16(p) && a16(g) && a16(m) && a16(v);   // vec4: the caller vouches that seg_start % 4 == 0
+  const bool clamp = clip_value > 0.f;
   const long work = vec ? n / 4 : n;
   const int grid = (int)((work + 255) / 256 > 4096 ? 4096 : (work + 255) / 256);
   const size_t lds = (size_t)n_seg * sizeof(long);
-  if (vec)
-    hipLaunchKernelGGL(k_adamw<true>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_lr_mult, seg_wd, n_seg,
-                       lr, beta1, beta2, eps, bc1, bc2s, grad_scale, zero_grad, skip, amp_state);
-  else
-    hipLaunchKernelGGL(k_adamw<false>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p, g, m, v, n, seg_start, seg_lr_mult, seg_wd, n_seg,
-                       lr, beta1, beta2, eps, bc1, bc2s, grad_scale, zero_grad, skip, amp_state);
+  hipStream_t st = (hipStream_t)stream;
+#define ADAMW_ARGS p, g, m, v, n, seg_start, seg_lr_mult, seg_wd, n_seg, lr, beta1, beta2, eps, bc1, bc2s, grad_scale, zero_grad, skip, amp_state, clip_coef, clip_value
+  if (vec && clamp) adamw_launch<true, true>(grid, lds, st, ADAMW_ARGS);
+  else if (vec) adamw_launch<true, false>(grid, lds, st, ADAMW_ARGS);
+  else if (clamp) adamw_launch<false, true>(grid, lds, st, ADAMW_ARGS);
+  else adamw_launch<false, false>(grid, lds, st, ADAMW_ARGS);
+#undef ADAMW_ARGS
   VFM_LAUNCH_CHECK();
   return VFM_OK;
 }

@@ -1404,15 +1404,48 @@ def postprocess_argmax(logits, window, flip, out_size, pred=None, label=None, hi
     return pred
 
 
-def adamw(p, g, m, v, seg_start, seg_lr_mult, seg_wd, lr, betas, eps, step, grad_scale=1.0, zero_grad=False, vec4=False, skip=None, amp_state=None):
+def adamw(p, g, m, v, seg_start, seg_lr_mult, seg_wd, lr, betas, eps, step, grad_scale=1.0, zero_grad=False, vec4=False, skip=None, amp_state=None,
+          clip_coef=None, clip_value=0.0):
     """skip: int32 device tensor [1]; non-zero = leave parameters and moments alone (loss-scaled training: the step's gradients overflowed).
-    amp_state: fp32 device tensor [4] {loss scale, growth tracker, steps taken, steps skipped}: un-scale and bias corrections from it."""
+    amp_state: fp32 device tensor [4] {loss scale, growth tracker, steps taken, steps skipped}: un-scale and bias corrections from it.
+    clip_coef: fp32 device tensor [1] (grad_norm()'s clip state [1:2]): the gradients are multiplied by it on top of grad_scale;
+    clip_value > 0: the un-scaled gradient is clamped to +-clip_value before the moments.  Either one selects vfm_adamw_clip; without
+    them the call is vfm_adamw_guarded, as before."""
     lib = L.load()
     assert skip is None or (skip.dtype == torch.int32 and skip.numel() == 1)
     assert amp_state is None or (amp_state.dtype == torch.float32 and amp_state.numel() == 4 and amp_state.is_contiguous())
-    L.check(lib.vfm_adamw_guarded(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(seg_start), L.ptr(seg_lr_mult),
-                                  L.ptr(seg_wd), seg_start.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), max(int(step), 1),
-                                  float(grad_scale), int(bool(zero_grad)), int(bool(vec4)), L.ptr(skip), L.ptr(amp_state), L.stream()), "vfm_adamw")
+    args = (L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(seg_start), L.ptr(seg_lr_mult),
+            L.ptr(seg_wd), seg_start.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), max(int(step), 1),
+            float(grad_scale), int(bool(zero_grad)), int(bool(vec4)), L.ptr(skip), L.ptr(amp_state))
+    if clip_coef is None and not clip_value > 0:
+        L.check(lib.vfm_adamw_guarded(*args, L.stream()), "vfm_adamw")
+        return
+    assert clip_coef is None or (clip_coef.dtype == torch.float32 and clip_coef.numel() == 1 and clip_coef.device == p.device)
+    L.check(lib.vfm_adamw_clip(*args, L.ptr(clip_coef), float(clip_value), L.stream()), "vfm_adamw_clip")
+
+
+NORM_KINDS = {2: 2, 1: 1, float("inf"): 0, "inf": 0}   # norm_type (2.0 and 1.0 hash as 2 and 1) -> VFM_NORM_L2 / VFM_NORM_L1 / VFM_NORM_INF
+
+
+def grad_norm(g, norm_type=2, max_norm=float("inf"), pre_scale=1.0, amp_state=None, clip_state=None, flag=None, workspace=None):
+    """vfm_grad_norm: norm of `pre_scale * g` (with amp_state: of `pre_scale / amp_state[0] * g`) over the flat fp32 buffer g and torch's
+    clip_grad_norm_ coefficient, left on the device: -> clip_state fp32 [4] {total norm, min(1, max_norm / (total + 1e-6)), 0, 0}.
+    flag: int32 [1], set to 1 when g holds an inf / NaN, else to 0.  workspace: float64 [4096] (allocated when not given).  No host read."""
+    lib = L.load()
+    if norm_type not in NORM_KINDS:
+        raise ValueError("grad_norm: norm_type %r (2, 1 and inf are the norms the kernel computes)" % (norm_type,))
+    assert g.dtype == torch.float32 and g.dim() == 1 and g.is_contiguous(), (g.dtype, g.shape)
+    if clip_state is None:
+        clip_state = torch.empty(4, dtype=torch.float32, device=g.device)
+    if workspace is None:
+        workspace = torch.empty(4096, dtype=torch.float64, device=g.device)
+    assert clip_state.dtype == torch.float32 and clip_state.numel() == 4 and clip_state.is_contiguous()
+    assert workspace.dtype == torch.float64 and workspace.numel() >= 4096 and workspace.is_contiguous()
+    assert flag is None or (flag.dtype == torch.int32 and flag.numel() == 1)
+    assert amp_state is None or (amp_state.dtype == torch.float32 and amp_state.numel() == 4 and amp_state.is_contiguous())
+    L.check(lib.vfm_grad_norm(L.ptr(g), g.numel(), NORM_KINDS[norm_type], float(max_norm), float(pre_scale), L.ptr(amp_state), L.ptr(workspace),
+                              L.ptr(clip_state), L.ptr(flag), L.stream()), "vfm_grad_norm")
+    return clip_state
 
 
 def amp_update(flag, amp_state, growth, backoff, interval, dynamic):

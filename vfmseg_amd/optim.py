@@ -145,18 +145,20 @@ class FusedAdamW:
             cuts[-1][2] = a + dict(zip(self.names, [p.numel() for p in self.params]))[nm]
         return [tuple(c) for c in cuts]
 
-    def step(self, lr=None, grad_scale=1.0, zero_grad=False, skip_flag=None, amp_state=None):
+    def step(self, lr=None, grad_scale=1.0, zero_grad=False, skip_flag=None, amp_state=None, clip_coef=None, clip_value=0.0):
         """zero_grad=True clears the flat gradient buffer in the same pass (OptimWrapper.update_params: step, then zero_grad).
         skip_flag / amp_state (AmpOptimWrapper, device tensors): a non-zero flag makes the launch a no-op on parameters and moments;
         with amp_state the loss scale and the step count of the bias corrections are read on the device and `step_count` is the
-        wrapper's to maintain (AmpOptimWrapper.sync)."""
+        wrapper's to maintain (AmpOptimWrapper.sync).
+        clip_coef (device scalar: ops.grad_norm's clip state [1:2]) / clip_value: OptimWrapper's clip_grad, consumed inside the launch."""
         if amp_state is None:
             self.step_count += 1
         PARAM_EPOCH[0] += 1  # the fused kernel rewrites the parameters behind torch's version counters
         lr = self.lr if lr is None else lr
         self.param_groups[0]["lr"] = lr
         ops.adamw(self.flat, self.gflat, self.m, self.v, self.seg_start, self.seg_lr, self.seg_wd, lr, self.betas, self.eps,
-                  self.step_count, grad_scale, zero_grad=zero_grad, vec4=True, skip=skip_flag, amp_state=amp_state)   # offsets are multiples of 16 floats
+                  self.step_count, grad_scale, zero_grad=zero_grad, vec4=True, skip=skip_flag, amp_state=amp_state,   # offsets are multiples of 16 floats
+                  clip_coef=clip_coef, clip_value=clip_value)
         self._grads_cleared = bool(zero_grad)
 
     def zero_grad(self):
@@ -182,12 +184,104 @@ class FusedAdamW:
         self.v.copy_(sd["v"])
 
 
-class OptimWrapper:
-    """mmengine OptimWrapper.update_params: backward -> (grad sync) -> step -> zero_grad; scheduler stepped by iter."""
+_INF = float("inf")
 
-    def __init__(self, optimizer, scheduler=None, grad_sync=None):
+
+def parse_clip_grad(clip_grad):
+    """mmengine OptimWrapper's `clip_grad` -> None | dict(type='norm', max_norm, norm_type) | dict(type='value', clip_value).
+    'norm' (the default type) is torch.nn.utils.clip_grad_norm_ with norm_type 2 (default), 1 or inf; 'value' is clip_grad_value_.
+    What the fused path does not implement is refused by the option's name - never dropped."""
+    if clip_grad is None:
+        return None
+    if not isinstance(clip_grad, dict):
+        raise TypeError("optim_wrapper.clip_grad must be None or a dict, got %r" % (clip_grad,))
+    cg = dict(clip_grad)
+    typ = cg.pop("type", "norm")
+    if typ == "value":
+        if "clip_value" not in cg:
+            raise ValueError("optim_wrapper.clip_grad: type='value' needs clip_value")
+        cv = float(cg.pop("clip_value"))
+        if cg:
+            raise NotImplementedError("optim_wrapper.clip_grad (type='value'): option %r is not supported (clip_value is the only one)" % sorted(cg)[0])
+        if not cv > 0:
+            raise ValueError("optim_wrapper.clip_grad.clip_value must be > 0, got %r" % (cv,))
+        return dict(type="value", clip_value=cv)
+    if typ != "norm":
+        raise NotImplementedError("optim_wrapper.clip_grad.type=%r ('norm' and 'value' are the two mmengine has)" % (typ,))
+    if "max_norm" not in cg:
+        raise ValueError("optim_wrapper.clip_grad: type='norm' needs max_norm")
+    max_norm = float(cg.pop("max_norm"))
+    nt = cg.pop("norm_type", 2)
+    if isinstance(nt, str) and nt.lower() in ("inf", "+inf", "infinity"):
+        nt = _INF
+    if isinstance(nt, bool) or not isinstance(nt, (int, float)) or float(nt) not in (1.0, 2.0, _INF):
+        raise NotImplementedError("optim_wrapper.clip_grad.norm_type=%r: the fused norm kernel computes the 2-, 1- and inf-norm" % (nt,))
+    if cg.pop("error_if_nonfinite", False):
+        raise NotImplementedError("optim_wrapper.clip_grad.error_if_nonfinite=True needs a host read of the norm at every step, which the "
+                                  "device-side clipping exists to avoid; read grad_norm() where the check is wanted")
+    if cg:
+        raise NotImplementedError("optim_wrapper.clip_grad: option %r is not supported (type, max_norm, norm_type, error_if_nonfinite=False)"
+                                  % sorted(cg)[0])
+    if not max_norm >= 0:   # (a NaN too)
+        raise ValueError("optim_wrapper.clip_grad.max_norm must be >= 0, got %r" % (max_norm,))
+    return dict(type="norm", max_norm=max_norm, norm_type=float(nt))
+
+
+class OptimWrapper:
+    """mmengine OptimWrapper.update_params: scale_loss -> backward -> [every accumulative_counts-th call: (grad sync) -> clip -> step ->
+    zero_grad]; scheduler stepped by iter.
+
+    clip_grad (parse_clip_grad): clipping happens inside step(), on the gradients as the optimiser sees them - after the data-parallel
+    average and, under AmpOptimWrapper, after the un-scale.  On the GPU nothing is read back: vfm_grad_norm leaves the norm and the
+    coefficient in a 4-float device tensor and the fused AdamW launch takes the coefficient from there; grad_norm() reads the last
+    total norm when asked to (one host wait).
+    accumulative_counts = N: gradients of N consecutive update_params calls add up in the flat buffer (each loss divided by N, the
+    last max_counts % N ones of a run by that remainder), the optimiser steps on every N-th call and on the run's last one.  `iter`
+    (the LR schedule) advances on every call, optimizer.step_count (the bias corrections) on real steps only; a step takes the
+    schedule's value at the iteration that performs it.  Under data parallelism the held micro-steps send nothing (mmengine's no_sync):
+    one set of all-reduces per window, over the accumulated buffer."""
+
+    def __init__(self, optimizer, scheduler=None, grad_sync=None, clip_grad=None, accumulative_counts=1):
         self.optimizer, self.scheduler, self.grad_sync = optimizer, scheduler, grad_sync
         self.iter = 0
+        self.clip_grad = parse_clip_grad(clip_grad)
+        if isinstance(accumulative_counts, bool) or not isinstance(accumulative_counts, int) or accumulative_counts < 1:
+            raise ValueError("optim_wrapper.accumulative_counts must be an integer >= 1, got %r" % (accumulative_counts,))
+        self._accumulative_counts = accumulative_counts
+        self._inner_count, self._max_counts, self._remainder_counts = 0, -1, -1
+        self._clip_state = self._clip_ws = self._clip_flag = None   # device side of the clipping (built at the first GPU step)
+        self._host_norm = None
+
+    # ---- gradient accumulation (mmengine OptimWrapper.initialize_count_status / should_update / scale_loss)
+    def initialize_count_status(self, init_counts, max_counts):
+        """Runner.train: the iteration the run (re)starts at and the one it ends at - the window bookkeeping of accumulative_counts."""
+        n = self._accumulative_counts
+        self._inner_count, self._max_counts = int(init_counts), int(max_counts)
+        if self._inner_count % n != 0:
+            import warnings
+            warnings.warn(f"Resumed iteration number {init_counts} is not divisible by accumulative_counts={n}: the gradients of the "
+                          "window that was open when the checkpoint was written are lost, and the first step comes early")
+        residual = self._max_counts - self._inner_count
+        self._remainder_counts = residual - residual // n * n
+
+    def should_update(self):
+        return self._inner_count % self._accumulative_counts == 0 or self._inner_count == self._max_counts
+
+    def _next_updates(self):
+        """Will the backward that is about to run complete a window?  (GradSync is told BEFORE backward: its buckets leave from hooks.)"""
+        nxt = self._inner_count + 1
+        return nxt % self._accumulative_counts == 0 or nxt == self._max_counts
+
+    def scale_loss(self, loss):
+        """mmengine OptimWrapper.scale_loss: loss / accumulative_counts, and in the last max_counts % accumulative_counts iterations of
+        a run loss / that remainder; the loss itself when accumulative_counts == 1."""
+        n = self._accumulative_counts
+        if n == 1:
+            return loss
+        if self._max_counts != -1 and self._inner_count >= self._max_counts - self._remainder_counts:
+            n = self._remainder_counts
+            assert n > 0, "update_params called past max_counts"
+        return loss / n
 
     @staticmethod
     def _backward(loss):
@@ -198,34 +292,77 @@ class OptimWrapper:
         from .functional import join_wgrad_stream
         join_wgrad_stream()   # the heads' weight gradients were issued on a side stream: everything below reads the flat gradient buffer
 
+    def _prepare(self, loss):
+        """What backward() runs on: the loss itself (AmpOptimWrapper: times the loss scale)."""
+        return loss
+
     def update_params(self, loss):
-        self._backward(loss)
-        if self.grad_sync is not None:
-            self.grad_sync()
-        lr = self.scheduler.lr(self.iter) if self.scheduler is not None else None
-        self.optimizer.step(lr, grad_scale=getattr(self.grad_sync, "post_scale", 1.0), zero_grad=True)
-        self.optimizer.zero_grad()
+        self.backward(self.scale_loss(loss))
+        if self.should_update():
+            self._step()
+            self.optimizer.zero_grad()
+        elif self.grad_sync is not None:
+            self.grad_sync()   # held (sends nothing): re-arms the buckets and the pending-backward count
         self.iter += 1
 
     # ---- the piecewise mmengine surface (DACS.train_step: two backward passes, then one step): update_params == backward + step + zero_grad
-    def scale_loss(self, loss):
-        """mmengine OptimWrapper.scale_loss with accumulative_counts == 1: the loss itself."""
-        return loss
-
     def backward(self, loss, **kw):
         """Gradients ACCUMULATE into the flat gradient buffer: a second call before step() adds to the first."""
-        self._backward(loss)
+        if self.grad_sync is not None and self._accumulative_counts != 1:
+            self.grad_sync.hold = not self._next_updates()
+        self._backward(self._prepare(loss))
+        self._inner_count += 1
 
     def step(self, **kw):
         """What update_params does after its backward, up to and including the fused clearing of the gradients."""
+        self._step()
+        self.iter += 1
+
+    def _step(self):
         if self.grad_sync is not None:
             self.grad_sync()
         lr = self.scheduler.lr(self.iter) if self.scheduler is not None else None
-        self.optimizer.step(lr, grad_scale=getattr(self.grad_sync, "post_scale", 1.0), zero_grad=True)
-        self.iter += 1
+        post = getattr(self.grad_sync, "post_scale", 1.0)
+        self.optimizer.step(lr, grad_scale=post, zero_grad=True, **self._clip(post))
 
     def zero_grad(self, **kw):
         self.optimizer.zero_grad()
+
+    # ---- clipping
+    def _clip(self, pre_scale, amp_state=None, flag=None, host_scale=1.0):
+        """-> the keyword arguments the optimiser's step takes for clip_grad ({} when it is off).
+        GPU: vfm_grad_norm over the flat buffer (norm of pre_scale [/ amp_state[0]] * g, coefficient and - `flag` - the non-finite flag
+        on the device) -> clip_coef for the fused AdamW launch; 'value': clip_value for it.
+        Host path (CPU tensors: the stub-optimiser tests): the same semantics from plain torch, applied to the buffer in place."""
+        cg = self.clip_grad
+        if cg is None:
+            return {}
+        g = self.optimizer.gflat
+        if g.is_cuda:
+            if cg["type"] == "value":
+                return dict(clip_value=cg["clip_value"])
+            if self._clip_state is None or self._clip_state.device != g.device:
+                self._clip_state = torch.zeros(4, dtype=torch.float32, device=g.device)
+                self._clip_ws = torch.empty(4096, dtype=torch.float64, device=g.device)
+            ops.grad_norm(g, cg["norm_type"], cg["max_norm"], pre_scale, amp_state, self._clip_state, flag, self._clip_ws)
+            return dict(clip_coef=self._clip_state[1:2])
+        s = pre_scale / host_scale
+        if cg["type"] == "value":
+            g.clamp_(-cg["clip_value"] / s, cg["clip_value"] / s)   # clamp(s g, +-c) = s clamp(g, +-c / s)
+            return {}
+        total = torch.linalg.vector_norm(g * s, cg["norm_type"])
+        self._host_norm = float(total)
+        g.mul_(torch.clamp(cg["max_norm"] / (total + 1e-6), max=1.0))   # clip_grad_norm_
+        return {}
+
+    def grad_norm(self):
+        """Total norm of the gradients of the last step, before clipping, as the optimiser saw them (averaged over ranks, un-scaled);
+        None when clip_grad is not type 'norm' or no step has run.  On the GPU this is the one host read clipping ever costs."""
+        if self.clip_grad is None or self.clip_grad["type"] != "norm":
+            return None
+        if self._clip_state is not None:
+            return float(self._clip_state[0].item())
+        return self._host_norm
 
     def get_lr(self):
         return self.optimizer.param_groups[0]["lr"]
@@ -253,8 +390,8 @@ class AmpOptimWrapper(OptimWrapper):
     _DTYPES = {None: torch.float16, "float16": torch.float16, "fp16": torch.float16, "half": torch.float16, torch.float16: torch.float16,
                "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, torch.bfloat16: torch.bfloat16}
 
-    def __init__(self, optimizer, scheduler=None, grad_sync=None, loss_scale="dynamic", dtype=None):
-        super().__init__(optimizer, scheduler, grad_sync)
+    def __init__(self, optimizer, scheduler=None, grad_sync=None, loss_scale="dynamic", dtype=None, clip_grad=None, accumulative_counts=1):
+        super().__init__(optimizer, scheduler, grad_sync, clip_grad=clip_grad, accumulative_counts=accumulative_counts)
         if dtype not in self._DTYPES:
             raise NotImplementedError("AmpOptimWrapper: autocast dtype %r (float16 and bfloat16 are the ones torch.autocast offers on a GPU)" % (dtype,))
         self.dtype = self._DTYPES[dtype]
@@ -276,44 +413,55 @@ class AmpOptimWrapper(OptimWrapper):
         else:
             raise TypeError("loss_scale must be 'dynamic', a number or a dict, got %r" % (loss_scale,))
 
-    def update_params(self, loss):
-        """GradScaler.scale(loss).backward(); unscale_; step (skipped on inf / NaN); update.
+    def _prepare(self, loss):
+        """GradScaler.scale(loss): on the GPU the factor is the DEVICE scale (built here at the first call); every micro-step of an
+        accumulation window multiplies by the same one, since the scale moves only in vfm_amp_update, after a step."""
+        g = self.optimizer.gflat
+        if not g.is_cuda:                    # host path (CPU tensors: tests of the schedule against torch's GradScaler)
+            return loss * self._scale
+        if self._state is None:
+            self._state = torch.tensor([self._scale, float(self._tracker), float(self.optimizer.step_count), float(self._skipped)],
+                                       dtype=torch.float32, device=g.device)
+        return loss * self._state[0]
+
+    def _step(self):
+        """unscale_; [clip]; step (skipped on inf / NaN); update - what follows GradScaler.scale(loss).backward() in update_params.
         On the GPU the scaler's state {scale, growth tracker, optimiser steps, skipped steps} lives in a 4-float DEVICE tensor: the loss
         is multiplied by the device scale, the overflow flag is formed on the device, the fused AdamW launch reads flag, scale and step
         count there (vfm_adamw_guarded) and vfm_amp_update applies GradScaler.update() - the host never waits for the backward pass
         (torch's GradScaler.step pays a found_inf.item() per step with a non-fused optimiser: the host then cannot run ahead of the
         GPU, which cost ~1 ms of a 15.3-ms step here).  `scale`, `skipped`, `growth_tracker` and optimizer.step_count are read back
-        on demand (sync())."""
+        on demand (sync()).
+        With clip_grad type 'norm' the norm pass (vfm_grad_norm) also forms the flag - one pass over the buffer where
+        isfinite(g.sum()) plus a norm would be two - and the norm is that of the UN-SCALED gradients."""
         g = self.optimizer.gflat
-        if not g.is_cuda:                    # host path (CPU tensors: tests of the schedule against torch's GradScaler)
-            self._backward(loss * self._scale)
-            if self.grad_sync is not None:
-                self.grad_sync()
-            found_inf = not bool(torch.isfinite(g.sum()).item())
+        norm_clip = self.clip_grad is not None and self.clip_grad["type"] == "norm"
+        if self.grad_sync is not None:
+            self.grad_sync()
+        post = getattr(self.grad_sync, "post_scale", 1.0)
+        lr = self.scheduler.lr(self.iter) if self.scheduler is not None else None
+        if not g.is_cuda:
+            found_inf = not bool((torch.isfinite(g).all() if norm_clip else torch.isfinite(g.sum())).item())
             flag = torch.tensor([int(found_inf)], dtype=torch.int32)
-            lr = self.scheduler.lr(self.iter) if self.scheduler is not None else None
-            self.optimizer.step(lr, grad_scale=getattr(self.grad_sync, "post_scale", 1.0) / self._scale, zero_grad=True, skip_flag=flag)
-            self.optimizer.zero_grad()
+            self._clip(post, host_scale=self._scale)
+            self.optimizer.step(lr, grad_scale=post / self._scale, zero_grad=True, skip_flag=flag)
             if found_inf:
                 self._skipped += 1
                 self.optimizer.step_count -= 1   # torch's AdamW does not count a skipped step (bias correction)
             self._update_scale(found_inf)
-            self.iter += 1
             return
-        if self._state is None:
-            self._state = torch.tensor([self._scale, float(self._tracker), float(self.optimizer.step_count), float(self._skipped)],
-                                       dtype=torch.float32, device=g.device)
-        self._backward(loss * self._state[0])
-        if self.grad_sync is not None:
-            self.grad_sync()
         # after the all-reduce every rank sees the same sums, hence the same decision (an inf / NaN survives the reduction)
-        flag = (~torch.isfinite(g.sum())).to(torch.int32).reshape(1)
-        lr = self.scheduler.lr(self.iter) if self.scheduler is not None else None
-        self.optimizer.step(lr, grad_scale=getattr(self.grad_sync, "post_scale", 1.0), zero_grad=True, skip_flag=flag, amp_state=self._state)
-        self.optimizer.zero_grad()
+        if norm_clip:
+            if self._clip_flag is None or self._clip_flag.device != g.device:
+                self._clip_flag = torch.zeros(1, dtype=torch.int32, device=g.device)
+            flag = self._clip_flag
+            kw = self._clip(post, amp_state=self._state, flag=flag)
+        else:
+            flag = (~torch.isfinite(g.sum())).to(torch.int32).reshape(1)
+            kw = self._clip(post)
+        self.optimizer.step(lr, grad_scale=post, zero_grad=True, skip_flag=flag, amp_state=self._state, **kw)
         ops.amp_update(flag, self._state, self.growth_factor, self.backoff_factor, self.growth_interval, self.dynamic)
         self._stale = True
-        self.iter += 1
 
     def sync(self):
         """Read the device-side scaler state back (one host wait): scale, growth tracker, skipped steps, optimizer.step_count."""
@@ -412,8 +560,9 @@ class PEFTOptimWrapperConstructor:
             sc.pop("by_epoch", None)
             sched = PolyLR(opt.lr, **sc)
         wtype = self.cfg.get("type", "OptimWrapper")
+        common = dict(clip_grad=self.cfg.get("clip_grad"), accumulative_counts=self.cfg.get("accumulative_counts", 1))
         if wtype == "AmpOptimWrapper":
-            return AmpOptimWrapper(opt, sched, loss_scale=self.cfg.get("loss_scale", "dynamic"), dtype=self.cfg.get("dtype"))
+            return AmpOptimWrapper(opt, sched, loss_scale=self.cfg.get("loss_scale", "dynamic"), dtype=self.cfg.get("dtype"), **common)
         if wtype != "OptimWrapper":
             raise NotImplementedError("optim_wrapper type %r (OptimWrapper and AmpOptimWrapper are the ones tools/train.py uses)" % (wtype,))
-        return OptimWrapper(opt, sched)
+        return OptimWrapper(opt, sched, **common)

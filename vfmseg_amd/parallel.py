@@ -89,7 +89,11 @@ class GradSync:
     """Averaging all-reduce of the flat gradient buffer in production-order buckets.
 
     `ready(i)` may be called from backward hooks as soon as bucket i is final (overlap on a side stream);
-    `finish()` (or calling the object) reduces whatever is still pending and joins the side stream."""
+    `finish()` (or calling the object) reduces whatever is still pending and joins the side stream.
+
+    `hold` (set by OptimWrapper before each backward of a gradient-accumulation window that does not end in a step - mmengine's
+    no_sync): ready() and finish() send nothing, the gradients stay local and keep adding up; the all-reduce runs once, on the
+    micro-step that updates, over the accumulated buffer.  finish() still re-arms the pending-backward count."""
 
     def __init__(self, gflat, buckets, group=None):
         self.gflat, self.buckets, self.group = gflat, buckets, group
@@ -100,11 +104,12 @@ class GradSync:
         self.done = [False] * len(buckets)
         self.works = []
         self.post_scale = (1.0 / self.world) if self.cuda else 1.0  # consumed by OptimWrapper -> vfm_adamw grad_scale
+        self.hold = False
         self.measure = False      # bench.py --gpus N: HIP events around the join in finish() (the all-reduce time backward did not hide)
         self._pairs = []
 
     def ready(self, i):
-        if not self.active or self.done[i]:
+        if not self.active or self.hold or self.done[i]:
             return
         _, a, b = self.buckets[i]
         sl = self.gflat[a:b]
@@ -119,7 +124,7 @@ class GradSync:
     def finish(self):
         for i in range(len(self.buckets)):
             self.ready(i)
-        if self.active:
+        if self.active and not self.hold:
             if self.cuda:
                 cur = torch.cuda.current_stream()
                 if self.measure:

@@ -259,8 +259,14 @@ def uda_rein_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint
     return cfg
 
 
-def optim_cfg():
+def optim_cfg(clip_grad=None, accumulative_counts=1):
+    """clip_grad / accumulative_counts: mmengine OptimWrapper's keys (vfmseg_amd.optim.OptimWrapper); the defaults leave them out."""
     embed_multi = dict(lr_mult=1.0, decay_mult=0.0)
+    extra = {}
+    if clip_grad is not None:
+        extra["clip_grad"] = dict(clip_grad)
+    if accumulative_counts != 1:
+        extra["accumulative_counts"] = accumulative_counts
     return dict(
         optim_wrapper=dict(
             constructor="PEFTOptimWrapperConstructor",
@@ -275,6 +281,7 @@ def optim_cfg():
                 },
                 norm_decay_mult=0.0,
             ),
+            **extra,
         ),
         param_scheduler=[dict(type="PolyLR", eta_min=0, power=0.9, begin=0, end=40000, by_epoch=False)],
     )

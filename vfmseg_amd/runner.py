@@ -281,6 +281,14 @@ class Runner:
         val_interval, val_begin = tc.get("val_interval"), tc.get("val_begin", 0) or 0
         os.makedirs(self.work_dir, exist_ok=True)
         log = open(os.path.join(self.work_dir, f"scalars_rank{self.rank}.jsonl"), "a") if self.rank == 0 else None
+        if hasattr(self.ow, "initialize_count_status"):   # gradient accumulation: where the run (re)starts and where its last window ends
+            self.ow.initialize_count_status(self.iter, max_iters)
+        acc = getattr(self.ow, "_accumulative_counts", 1)
+        if acc != 1 and ckpt_interval and ckpt_interval % acc != 0 and self.rank == 0:
+            import warnings
+            warnings.warn(f"checkpoint interval {ckpt_interval} is not a multiple of accumulative_counts={acc}: a checkpoint written inside "
+                          "an accumulation window does not hold the window's partial gradient sums, a resume from it loses them")
+        log_norm = getattr(self.ow, "clip_grad", None) is not None and self.ow.clip_grad["type"] == "norm"
         t0 = time.time()
         while self.iter < max_iters:
             data = next(self.loader)
@@ -290,6 +298,9 @@ class Runner:
                 rec = {k: float(v.detach() if torch.is_tensor(v) else v) for k, v in out.items() if v is not None}  # one sync per log interval
                 rec.update(iter=self.iter, lr=self.ow.get_lr(), time=(time.time() - t0) / log_interval,
                            memory=torch.cuda.max_memory_allocated() // (1 << 20))
+                gn = self.ow.grad_norm() if log_norm else None
+                if gn is not None:
+                    rec["grad_norm"] = gn   # of the LAST optimiser step (mmengine logs this key as a window mean)
                 t0 = time.time()
                 if log:
                     log.write(json.dumps(rec) + "\n")

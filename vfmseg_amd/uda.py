@@ -161,6 +161,10 @@ class DACS(EncoderDecoder):
         if isinstance(optim_wrapper, AmpOptimWrapper) or getattr(optim_wrapper, "grad_sync", None) is not None:
             raise NotImplementedError("DACS: --amp (AmpOptimWrapper) and data parallelism are not supported: two backward passes per step do not "
                                       "fit the loss scaler's and GradSync's one-backward step")
+        if getattr(optim_wrapper, "_accumulative_counts", 1) != 1:
+            raise NotImplementedError(f"DACS: optim_wrapper.accumulative_counts={optim_wrapper._accumulative_counts} has no meaning here: the "
+                                      "reference's DACS.train_step calls step() and zero_grad() unconditionally after its two backward "
+                                      "passes (clip_grad works: it is applied inside step())")
         self.mean, self.std = self.data_preprocessor.mean, self.data_preprocessor.std
         img = self.data_preprocessor(data["img"], True)
         target_img = self.data_preprocessor(data["target_img"], True)
