@@ -535,6 +535,30 @@ int vfm_adamw_clip(float* p, float* g, float* m, float* v, long n, const long* s
                    int zero_grad, int vec4, const int* skip, const float* amp_state, const float* clip_coef, float clip_value,
                    void* stream);
 
+/* ---- Dice loss on the fused loss path (ABI 11; csrc/dice.hip; mmseg 1.2.2 losses/dice_loss.py; fp32 / int64 / int32 in both builds) ----
+ * With v = bilinear_up(logits_low) (align_corners=False; logits_low fp32 NHWC [B,h,w,C], C <= 32, h <= H, w <= W), p = sigmoid(v)
+ * (use_sigmoid != 0) or softmax(v) over the classes, t[n,c,i] = [clamp(label[n,i], 0, C) == c] for c < C (a label >= C, 255 included, is an
+ * all-zero row whose pixel stays in the sums of p; a negative label is class 0) and per image n, over every pixel and every class but
+ * drop_class (-1: none; mmseg's DiceLoss(ignore_index=) names a class CHANNEL):
+ *     a = sum p t;   plain: b = sum p^2 + eps, c = sum t + eps, s = b + c, d = 2a / s;   naive: b = sum p, c = sum t, s = b + c + eps, d = (2a + eps) / s
+ *     loss = mean_n (1 - d_n);   d loss_n / d p = alpha t + beta p + gamma,  plain (-2/s, 4a/s^2, 0),  naive (-2/s, 0, (2a + eps)/s^2)
+ * The full-resolution logits never touch memory, no floating-point atomics, every sum in a fixed order: bitwise reproducible.
+ * vfm_upsample_dice_sums: every pixel of [H,W] once; block j of image n (grid B * nblk, nblk >= 1 chosen by the caller) leaves the sums of
+ *   its pixels in fsum [B,nblk,2] = (sum p t, sum p^2 | naive: sum p) and isum [B,nblk,3] = (sum t, valid, hits): valid = #(label !=
+ *   ignore_label), hits = #(valid and arg-max v == label), the counters of vfm_upsample_ce (mmseg `accuracy`).  Every row is written.
+ * vfm_dice_finish: ONE block adds the rows of every image in a fixed order, in double, and writes coef [B,3] = (alpha, beta, gamma) (the
+ *   factor loss_weight / B is NOT folded in), loss[0], acc[0] = 100 hits / (valid + acc_eps), and, where not NULL, sums [B,4] = (a, sum p^2 |
+ *   sum p, sum t, d_n) and counts [2] = (hits, valid) over the batch.  Nothing is read on the host.
+ * vfm_upsample_dice_bwd: the gather of vfm_upsample_ce - the waves of a low-resolution pixel walk the pixels of [H,W] whose bilinear footprint
+ *   touches it, activate them again and add their share of scale * d loss_n / d v with coef read on the device (scale = loss_weight / B).
+ *   dlogits [B,h,w,C] is written, or added to when accumulate != 0 (a cross-entropy gradient that is already there). */
+int vfm_upsample_dice_sums(const float* logits_low, const int64_t* label, int B, int h, int w, int C, int H, int W, int use_sigmoid,
+                           int naive, int drop_class, int ignore_label, int nblk, float* fsum, int32_t* isum, void* stream);
+int vfm_dice_finish(const float* fsum, const int32_t* isum, int B, int nblk, int naive, float eps, float acc_eps, float* coef, float* sums,
+                    int32_t* counts, float* loss, float* acc, void* stream);
+int vfm_upsample_dice_bwd(const float* logits_low, const int64_t* label, const float* coef, int B, int h, int w, int C, int H, int W,
+                          int use_sigmoid, int drop_class, float scale, int accumulate, float* dlogits, void* stream);
+
 /* ---- launch plans -------------------------------------------------------------------------------------- */
 /* A recorded sequence of the calls above, replayed in order on one stream by ONE call.  The hot path's backbone is a fixed launch
  * sequence per step (18 launches per transformer block: rein/models/backbones/dino_v2.py:259-291 forward_features and its backward) over

@@ -99,13 +99,27 @@ class Config(ConfigDict):
             cur[parts[-1]] = _wrap(val)
 
 
+def _option_value(node):
+    """A python literal in which `dict(k=v, ...)` may stand for {'k': v, ...}, as config files write their dicts."""
+    if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "dict" and not node.args \
+            and all(kw.arg is not None for kw in node.keywords):
+        return {kw.arg: _option_value(kw.value) for kw in node.keywords}
+    if isinstance(node, ast.List):
+        return [_option_value(e) for e in node.elts]
+    if isinstance(node, ast.Tuple):
+        return tuple(_option_value(e) for e in node.elts)
+    if isinstance(node, ast.Dict):
+        return {_option_value(k): _option_value(v) for k, v in zip(node.keys, node.values)}
+    return ast.literal_eval(node)
+
+
 def parse_cfg_options(items):
-    """['a.b=1', 'c=[1,2]', 'd=str'] -> dict (mmengine DictAction subset)."""
+    """['a.b=1', 'c=[1,2]', 'd=str', "e=[dict(type='X',w=1.0)]"] -> dict (mmengine DictAction subset; dict(...) calls of literals as well)."""
     out = {}
     for it in items or []:
         k, v = it.split("=", 1)
         try:
-            out[k] = ast.literal_eval(v)
+            out[k] = _option_value(ast.parse(v.strip(), mode="eval").body)
         except Exception:
             out[k] = v
     return out

@@ -925,6 +925,31 @@ class UpsampleCENormFn(torch.autograd.Function):
         return g, None, None, None, None, None
 
 
+class UpsampleDiceFn(torch.autograd.Function):
+    """loss = loss_weight * mean over the images of (1 - dice_n) of bilinear_up(logits_low) - mmseg 1.2.2 DiceLoss(reduction='mean') - and the
+    accuracy of mmseg `accuracy` from the same pass.  The full-resolution logits are never materialised.  drop_class: the
+    class channel DiceLoss(ignore_index=) leaves out (-1: none); ignore_label: the label the accuracy skips."""
+
+    @staticmethod
+    def forward(ctx, logits_low, label, use_sigmoid, naive, eps, drop_class, loss_weight, ignore_label=255):
+        loss, acc, _, dl = ops.upsample_dice(logits_low.contiguous(), label, use_sigmoid, naive, eps, drop_class, need_grad=True,
+                                             ignore_index=ignore_label)
+        ctx.save_for_backward(dl)
+        ctx.lw = loss_weight
+        ctx.mark_non_differentiable(acc)
+        if loss_weight != 1.0:
+            ops.axpby(loss, loss_weight, loss, 0.0)
+        return loss.view(()), acc
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        (g,) = ctx.saved_tensors
+        ops.scale_by_device_scalar(g, dloss.contiguous().view(1))
+        if ctx.lw != 1.0:
+            ops.axpby(g, ctx.lw, g, 0.0)
+        return g, None, None, None, None, None, None, None
+
+
 class UpsampleCEAllFn(torch.autograd.Function):
     """UpsampleCEFn with the accuracy of rein/models/heads/utils.py:35-80 (the HRDA head's): 100 * correct / label.numel() - ignored
     pixels stay in the denominator and count as wrong.  Same fused kernel; the raw (hits, valid) counters are finished here."""

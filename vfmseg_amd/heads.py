@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import functional as Fh
 from . import ops
+from .dice_loss import DiceLoss
 from .loss_options import loss_with_options
 from .precision import compute_dtype, is_half
 from .registry import MODELS
@@ -94,11 +95,17 @@ class CrossEntropyLoss(nn.Module):
 
 
 def loss_options_named(head_cfg):
-    """The loss options a decode head's config turns on, by name: 'sampler', 'class_weight', 'avg_non_ignore'."""
+    """The loss options a decode head's config turns on, by name: 'sampler', 'class_weight', 'avg_non_ignore', and, of a multi-loss
+    config, 'loss_decode list' (a list or tuple of losses) and 'DiceLoss' (an entry of that type, in a list or alone)."""
     named = ["sampler"] if head_cfg.get("sampler") is not None else []
     ld = head_cfg.get("loss_decode") or {}
-    if isinstance(ld, dict):
-        named += [k for k in ("class_weight", "avg_non_ignore") if ld.get(k)]
+    if isinstance(ld, (list, tuple)):
+        named.append("loss_decode list")
+    for entry in (ld if isinstance(ld, (list, tuple)) else [ld]):
+        if isinstance(entry, dict):
+            named += [k for k in ("class_weight", "avg_non_ignore") if entry.get(k) and k not in named]
+            if entry.get("type") == "DiceLoss" and "DiceLoss" not in named:
+                named.append("DiceLoss")
     return named
 
 
@@ -118,7 +125,18 @@ class BaseDecodeHead(nn.Module):
         self.out_channels = out_channels or num_classes
         if align_corners:
             raise NotImplementedError("align_corners=True is not on the HIP path (all reference configs use False)")
-        self.loss_decode = MODELS.build(loss_decode)
+        if isinstance(loss_decode, (list, tuple)):   # mmseg: one loss module per entry, summed per loss_name in loss_by_feat
+            if len(loss_decode) == 0:
+                raise ValueError("loss_decode: an empty list of losses")
+            self.loss_decode = nn.ModuleList([MODELS.build(ld) for ld in loss_decode])
+        else:
+            self.loss_decode = MODELS.build(loss_decode)
+        if any(isinstance(ld, DiceLoss) for ld in self._loss_modules()):
+            if self.out_channels == 1:
+                raise NotImplementedError("DiceLoss with out_channels == 1 (mmseg's binary form, which skips the one-hot expansion) is not implemented")
+            if sampler is not None:
+                raise NotImplementedError("DiceLoss together with sampler=: a pixel sampler hands the loss a per-pixel seg_weight, which mmseg's "
+                                          "DiceLoss cannot take (it asserts on the weight's shape); remove the sampler or the DiceLoss entry")
         self.sampler = MODELS.build(sampler, context=self) if sampler is not None else None
         self.conv_seg = nn.Conv2d(channels, self.out_channels, kernel_size=1)
         nn.init.normal_(self.conv_seg.weight, std=0.01)
@@ -127,20 +145,44 @@ class BaseDecodeHead(nn.Module):
     def _stack_batch_gt(self, batch_data_samples):
         return torch.stack([d.gt_sem_seg.data for d in batch_data_samples], dim=0)
 
-    def _ce(self, logits_nhwc, label, seg_weight=None):
+    def _loss_modules(self):
+        return list(self.loss_decode) if isinstance(self.loss_decode, nn.ModuleList) else [self.loss_decode]
+
+    def _ce(self, logits_nhwc, label, seg_weight=None, ld=None):
         """(loss, acc_seg) under the head's sampler and the loss module's options; without any, exactly the calls made before they existed."""
-        ld = self.loss_decode
+        ld = self.loss_decode if ld is None else ld
         if self.sampler is not None and seg_weight is not None:
             raise ValueError("loss_by_feat: seg_weight and sampler= would both set the pixel weights; give one of them")
         return loss_with_options(logits_nhwc, label, self.ignore_index, ld.loss_weight, self.sampler,
                                  ld.class_weight_on(logits_nhwc.device, logits_nhwc.shape[-1]), ld.avg_non_ignore, seg_weight)
 
+    def _losses(self, logits_nhwc, label, seg_weight=None):
+        """{loss_name: loss, ..., 'acc_seg'}.  A single CrossEntropyLoss (a dict loss_decode) is one _ce call, as before lists existed.
+        Otherwise one loss per entry, entries that share a loss_name added (mmseg loss_by_feat); acc_seg is the first cross-entropy
+        entry's, else the Dice kernels' (the same counters)."""
+        if isinstance(self.loss_decode, CrossEntropyLoss):
+            loss, acc = self._ce(logits_nhwc, label, seg_weight)
+            return {self.loss_decode.loss_name: loss, "acc_seg": acc}
+        if seg_weight is not None and any(isinstance(ld, DiceLoss) for ld in self._loss_modules()):
+            raise NotImplementedError("DiceLoss together with seg_weight: mmseg's DiceLoss cannot take a per-pixel weight (it asserts on "
+                                      "the weight's shape); the weighted losses (DACS) run with CrossEntropyLoss alone")
+        losses, acc_ce, acc_dice = {}, None, None
+        for ld in self._loss_modules():
+            if isinstance(ld, DiceLoss):
+                loss, acc = ld.loss_lowres(logits_nhwc, label, self.ignore_index)
+                acc_dice = acc if acc_dice is None else acc_dice
+            else:
+                loss, acc = self._ce(logits_nhwc, label, seg_weight, ld)
+                acc_ce = acc if acc_ce is None else acc_ce
+            losses[ld.loss_name] = loss if ld.loss_name not in losses else losses[ld.loss_name] + loss
+        losses["acc_seg"] = acc_ce if acc_ce is not None else acc_dice
+        return losses
+
     # ---- shared loss path (linear_head.py:72-113 / VFMHead.py:91-133)
     def _loss_from_lowres(self, logits_nhwc, seg_label, return_logits):
         label = seg_label.squeeze(1).contiguous()
         # loss and accuracy (mmseg `accuracy`: 100 * correct / (valid + eps)) come out of the fused kernel pair
-        loss, acc = self._ce(logits_nhwc, label)
-        losses = {self.loss_decode.loss_name: loss, "acc_seg": acc}
+        losses = self._losses(logits_nhwc, label)
         if return_logits:
             B, h, w, C = logits_nhwc.shape
             H, W = label.shape[1:]
@@ -153,8 +195,7 @@ class BaseDecodeHead(nn.Module):
         """mmseg BaseDecodeHead.loss_by_feat on the low-resolution NHWC logits: {loss_name, acc_seg}.  seg_weight fp32 [B,H,W] weighs every
         pixel's loss term (DACS's mix_weight); the accuracy is unweighted."""
         label = (seg_label.squeeze(1) if seg_label.dim() == 4 else seg_label).contiguous()
-        loss, acc = self._ce(seg_logits_nhwc, label, seg_weight)
-        return {self.loss_decode.loss_name: loss, "acc_seg": acc}
+        return self._losses(seg_logits_nhwc, label, seg_weight)
 
     def predict_by_feat(self, seg_logits_nhwc, batch_img_metas):
         m = batch_img_metas[0]

@@ -1180,6 +1180,52 @@ def ohem_weight(logits_low, label, thresh, k_request, ignore_index=255, class_we
     return weight, p, t, state, norm, counts
 
 
+def dice_blocks(H, W):
+    """Rows per image of the Dice sums' slab: one block of 256 threads per 1024 pixels, at most 1024 of them (a function of the map size alone)."""
+    return max(1, min(1024, (H * W + 1023) // 1024))
+
+
+def upsample_dice(logits_low, label, use_sigmoid=True, naive=False, eps=1e-3, drop_class=-1, need_grad=True, ignore_index=255,
+                  grad_scale=None, accumulate_into=None, stats=None):
+    """Dice loss (mmseg 1.2.2 DiceLoss, reduction 'mean', loss_weight 1) of bilinear_up(logits_low) against label, the full-resolution
+    logits never in memory (vfm_upsample_dice_sums -> vfm_dice_finish -> vfm_upsample_dice_bwd).
+    logits_low fp32 [B,h,w,C] NHWC; label int64 [B,H,W].  Returns (loss[1], acc[1], coef [B,3], dlogits or None): coef = (alpha, beta,
+    gamma) of d loss_n / d p = alpha t + beta p + gamma per image, dlogits = d loss / d logits_low * grad_scale (default 1 / B, the mean
+    over the images).  drop_class: a class channel left out of every sum (-1: none).  ignore_index only names the label that the accuracy
+    skips (mmseg `accuracy`); the loss knows no ignored label.  accumulate_into: an fp32 [B,h,w,C] gradient the Dice gradient is ADDED to
+    (it is then the returned dlogits).  stats: a dict that receives 'sums' fp32 [B,4] = (a, sum p^2 | sum p, sum t, d) and 'counts' int32 [2] =
+    (hits, valid)."""
+    lib = L.load()
+    B, h, w, Cc = logits_low.shape
+    _, H, W = label.shape
+    dev = logits_low.device
+    assert logits_low.dtype == torch.float32 and logits_low.is_contiguous() and label.dtype == torch.int64 and label.is_contiguous()
+    assert label.shape[0] == B
+    nblk = dice_blocks(H, W)
+    fsum = torch.empty(B, nblk, 2, dtype=torch.float32, device=dev)
+    isum = torch.empty(B, nblk, 3, dtype=torch.int32, device=dev)
+    L.check(lib.vfm_upsample_dice_sums(L.ptr(logits_low), L.ptr(label), B, h, w, Cc, H, W, int(bool(use_sigmoid)), int(bool(naive)),
+                                       int(drop_class), int(ignore_index), nblk, L.ptr(fsum), L.ptr(isum), L.stream()),
+            "vfm_upsample_dice_sums")
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    coef = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    sums = counts = None
+    if stats is not None:
+        sums = stats["sums"] = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        counts = stats["counts"] = torch.empty(2, dtype=torch.int32, device=dev)
+    acc_eps = float(torch.finfo(torch.float32).eps)
+    L.check(lib.vfm_dice_finish(L.ptr(fsum), L.ptr(isum), B, nblk, int(bool(naive)), float(eps), acc_eps, L.ptr(coef), L.ptr(sums),
+                                L.ptr(counts), L.ptr(out), L.ptr(out[1:]), L.stream()), "vfm_dice_finish")
+    dl = None
+    if need_grad:
+        dl = accumulate_into if accumulate_into is not None else torch.empty_like(logits_low)
+        assert dl.dtype == torch.float32 and dl.is_contiguous() and dl.shape == logits_low.shape
+        L.check(lib.vfm_upsample_dice_bwd(L.ptr(logits_low), L.ptr(label), L.ptr(coef), B, h, w, Cc, H, W, int(bool(use_sigmoid)),
+                                          int(drop_class), float(1.0 / B if grad_scale is None else grad_scale),
+                                          int(accumulate_into is not None), L.ptr(dl), L.stream()), "vfm_upsample_dice_bwd")
+    return out[0:1], out[1:2], coef, dl
+
+
 def pseudo_label(logits_low, size, thr, count, want_prob=False):
     """Teacher logits fp32 NHWC [B,h,w,C] -> (pseudo_label int64 [B,H,W], pseudo_prob fp32 [B,H,W] or None) at size = (H, W): bilinear
     (align_corners=False) + softmax + torch.max in registers; count (int32 [1], device) += #pixels with max prob >= thr."""

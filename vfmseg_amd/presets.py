@@ -23,6 +23,13 @@ _PREPROC = dict(
 _CE = dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)
 
 
+def ce_dice_loss(ce=1.0, dice=3.0, **dice_opts):
+    """mmseg's stock multi-loss loss_decode: cross-entropy plus DiceLoss; dice_opts go to DiceLoss (use_sigmoid, naive_dice,
+    eps, ignore_index).  Use it as a head's loss_decode: presets.segformer_head()['loss_decode'] = presets.ce_dice_loss()."""
+    return [dict(type="CrossEntropyLoss", loss_name="loss_ce", use_sigmoid=False, loss_weight=ce),
+            dict(type="DiceLoss", loss_name="loss_dice", loss_weight=dice, **dice_opts)]
+
+
 def dinov2_backbone(depth=24, embed_dim=1024, num_heads=16, img_size=512):
     return dict(
         type="DinoVisionTransformer",

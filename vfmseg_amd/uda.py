@@ -60,6 +60,10 @@ class DACS(EncoderDecoder):
         if dict(cfg["decode_head"]).get("sampler") is not None:
             raise NotImplementedError("DACS: decode_head sampler=: the mixed-image loss passes seg_weight (the pseudo-label weight), and a pixel "
                                       "sampler would set the same weights (mmseg lets the sampler overwrite them); remove the sampler")
+        ld = dict(cfg["decode_head"]).get("loss_decode")
+        if isinstance(ld, (list, tuple)) or (isinstance(ld, dict) and ld.get("type") == "DiceLoss"):
+            raise NotImplementedError("DACS: decode_head loss_decode list / DiceLoss: the mixed-image loss passes seg_weight (the pseudo-label "
+                                      "weight), which mmseg's DiceLoss cannot take; the self-training loop runs with one CrossEntropyLoss")
         super().__init__(backbone=cfg["backbone"], decode_head=cfg["decode_head"], train_cfg=cfg.get("train_cfg"),
                          test_cfg=cfg.get("test_cfg"), data_preprocessor=cfg.get("data_preprocessor"))
         self.local_iter = 0   # a plain attribute, as in the reference: a resumed run starts at 0 and re-initialises the teacher from the student
