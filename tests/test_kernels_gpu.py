@@ -214,7 +214,11 @@ def test_rope_vector_path():
 
 @pytest.mark.parametrize("C,ld", [(2730, 2752), (1366, 1366), (2731, 2752)])
 def test_layernorm_wide_ragged(C, ld):
-    """EVA02's SwiGLU sub-LN: C = 2730 columns inside 2752-wide buffers (pair-vectorised kernels); odd C takes the scalar path."""
+    """EVA02's SwiGLU sub-LN.  By the dispatchers of csrc/norm.hip: at (2730, 2752) and the odd (2731, 2752) the calls whose operands all
+    sit in the 2752-wide buffers (the 16-bit forward, both backwards) take the padded-pitch kernels k_ln_fwd_v4t / k_ln_bwd_v4t (the pitch
+    is a multiple of 4 and covers the partly valid last piece); the float32 forward writes a contiguous y of pitch C and so takes the
+    pair-vectorised k_ln_fwd_v2 at C = 2730 and the scalar k_ln_fwd<float, 48> at C = 2731.  (1366, 1366), whose pitch is only even,
+    takes k_ln_fwd_v2 / k_ln_bwd_v2 throughout.  No backward here reaches the scalar kernel (tests/test_norm_gpu.py does)."""
     rows = 70
     x = rnd(rows, C, seed=24, scale=1.5) + 0.3
     w, b = rnd(C, seed=25) * 0.1 + 1, rnd(C, seed=26) * 0.1

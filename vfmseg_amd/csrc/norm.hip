@@ -2,11 +2,14 @@
 #include "common.h"
 
 __device__ __forceinline__ float act_f(float v, int act) {
-  return act == VFM_ACT_GELU ? gelu_f(v) : (act == VFM_ACT_RELU ? fmaxf(v, 0.f) : v);
+  return act == VFM_ACT_GELU ? gelu_f(v) : (act == VFM_ACT_RELU ? fmaxf(v, 0.f) : (act == VFM_ACT_QGELU ? qgelu_f(v) : v));
 }
 __device__ __forceinline__ float act_grad_f(float v, int act) {
-  return act == VFM_ACT_GELU ? gelu_grad_f(v) : (act == VFM_ACT_RELU ? (v > 0.f ? 1.f : 0.f) : 1.f);
+  return act == VFM_ACT_GELU ? gelu_grad_f(v)
+                             : (act == VFM_ACT_RELU ? (v > 0.f ? 1.f : 0.f) : (act == VFM_ACT_QGELU ? qgelu_grad_f(v) : 1.f));
 }
+// the activations the GroupNorm / BatchNorm entries fuse: anything else is refused before a launch (act_f would fall through to identity)
+static inline bool norm_act_ok(int act) { return act >= VFM_ACT_NONE && act <= VFM_ACT_QGELU; }
 
 // =============================================================================================== LayerNorm
 // one wave per row; C <= 64*32; two-pass statistics in registers (matches torch's accuracy class)
@@ -765,6 +768,7 @@ __global__ void k_gn_apply(const float* __restrict__ x, const float* __restrict_
 extern "C" int vfm_groupnorm_fwd(const float* x, const float* w, const float* b, float eps, int G, int act, void* y, int y_dt,
                                  float* stats, float* ws_in, long B, long P, long C, void* stream) {
   VFM_CHECK(G > 0 && C % G == 0 && ws_in, VFM_E_SHAPE, "vfm_groupnorm_fwd: C %% G / ws");
+  VFM_CHECK(norm_act_ok(act), VFM_E_INVAL, "vfm_groupnorm_fwd: act=%d is not one of VFM_ACT_NONE / GELU / RELU / QGELU", act);
   if (B * P * C == 0) return VFM_OK;
   hipStream_t s = (hipStream_t)stream;
   const int nchunk = pick_chunks(P);
@@ -842,6 +846,7 @@ extern "C" int vfm_groupnorm_bwd(const void* dy, int dy_dt, const float* x, cons
                                  const float* stats, int G, int act, float* dx, float* dw, float* db, float* ws, long B,
                                  long P, long C, void* stream) {
   VFM_CHECK(G > 0 && C % G == 0 && ws, VFM_E_SHAPE, "vfm_groupnorm_bwd: args");
+  VFM_CHECK(norm_act_ok(act), VFM_E_INVAL, "vfm_groupnorm_bwd: act=%d is not one of VFM_ACT_NONE / GELU / RELU / QGELU", act);
   if (B * P * C == 0) return VFM_OK;
   hipStream_t s = (hipStream_t)stream;
   const int nchunk = pick_chunks(P);
@@ -1109,6 +1114,7 @@ __global__ void k_bn_apply(const float* __restrict__ x, const float* __restrict_
 }
 extern "C" int vfm_bn_apply(const float* x, const float* mean_var, const float* w, const float* b, float eps, int act, void* y,
                             int y_dt, long rows, long C, void* stream) {
+  VFM_CHECK(norm_act_ok(act), VFM_E_INVAL, "vfm_bn_apply: act=%d is not one of VFM_ACT_NONE / GELU / RELU / QGELU", act);
   const long total = rows * C;
   if (total == 0) return VFM_OK;
   const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
@@ -1123,6 +1129,7 @@ extern "C" int vfm_bn_bwd_reduce(const void* dy, int dy_dt, const float* x, cons
                                  const float* b, float eps, int act, float* sums_dy, float* ws, long rows, long C,
                                  void* stream) {
   VFM_CHECK(ws && sums_dy, VFM_E_INVAL, "vfm_bn_bwd_reduce: args");
+  VFM_CHECK(norm_act_ok(act), VFM_E_INVAL, "vfm_bn_bwd_reduce: act=%d is not one of VFM_ACT_NONE / GELU / RELU / QGELU", act);
   hipStream_t s = (hipStream_t)stream;
   const int nchunk = pick_chunks(rows);
   const int rpc = (int)((rows + nchunk - 1) / nchunk);
@@ -1153,6 +1160,7 @@ __global__ void k_bn_bwd_apply(const TD* __restrict__ dy, const float* __restric
 extern "C" int vfm_bn_bwd_apply(const void* dy, int dy_dt, const float* x, const float* mean_var, const float* w,
                                 const float* b, float eps, int act, const float* sums_dy, float total_rows, float* dx,
                                 long rows, long C, void* stream) {
+  VFM_CHECK(norm_act_ok(act), VFM_E_INVAL, "vfm_bn_bwd_apply: act=%d is not one of VFM_ACT_NONE / GELU / RELU / QGELU", act);
   const long total = rows * C;
   if (total == 0) return VFM_OK;
   const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
