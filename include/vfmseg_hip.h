@@ -559,6 +559,30 @@ int vfm_dice_finish(const float* fsum, const int32_t* isum, int B, int nblk, int
 int vfm_upsample_dice_bwd(const float* logits_low, const int64_t* label, const float* coef, int B, int h, int w, int C, int H, int W,
                           int use_sigmoid, int drop_class, float scale, int accumulate, float* dlogits, void* stream);
 
+/* ---- full fine-tuning of the backbone (ABI 12; csrc/fullft.hip; the same in both builds, VFM_BF16 = the half type) ----
+ * vfm_branch_param_grads : parameter gradients of a residual branch  x_out = x_in + gamma * (y W^T + b)  (LayerScale, dino_v2.py
+ *   layer_scale.py:20-27 behind attn.proj / mlp.fc2) from ONE read pass over dx (fp32 [M, D]) and the saved pre-scale branch output
+ *   u (fp32 | half [M, D]):
+ *       dgamma[c] (+)= sum_m dx[m,c] u[m,c]        dbias[c] (+)= gamma[c] sum_m dx[m,c]        t[m,c] = cast(dx[m,c] gamma[c])  (t may be NULL)
+ *   t (fp32 | half, the dgrad GEMM's operand) is what vfm_cast(dx, t, gamma) writes, bit for bit.  gamma is never divided by: a zero entry
+ *   gives dbias = 0 and an exact dgamma.  D % 64 == 0, every leading dimension a multiple of 8 elements, bases 16-byte aligned; M is free.
+ *   dgamma / dbias may each be NULL.  Two launches: per-block partial sums of a fixed row assignment (fp32; a block's 32 row lanes meet
+ *   pairwise in LDS), then one thread per column adds the blocks' rows in order in double.  No atomics: the same inputs give the same bits.
+ *   ws: VFM_BRANCH_WS_PARTS * 2 * D floats, contents irrelevant on entry. */
+enum { VFM_BRANCH_WS_PARTS = 128 };
+int vfm_branch_param_grads(const float* dx, long ld_dx, const void* u, int u_dt, long ld_u, const float* gamma, long M, long D,
+                           float* dgamma, float* dbias, int accumulate, void* t, int t_dt, long ld_t, float* ws, void* stream);
+/* vfm_pack_weights : the per-step refresh of the packed GEMM operands of ALL trained 2-D weights from the optimiser's fp32 master, one
+ *   launch whatever the depth:  w[n*ld_w + k] = cast(src[n*K + k])  and, where wt is not NULL,  wt[k*ld_wt + n] = cast(src[n*K + k])
+ *   for n < N, k < K (the dgrad GEMM's transposed image).  Pad columns / rows of the images are not touched.  The table is an array of
+ *   `nsites` entries in DEVICE memory; dt = dtype of the images; max_tiles = max over sites of ceil(N/64) * ceil(K/64).  The values are
+ *   those of vfm_cast / vfm_transpose (one RNE conversion of the fp32 value). */
+typedef struct vfm_pack_site {
+  const float* src; void* w; void* wt;
+  long N, K, ld_w, ld_wt;
+} vfm_pack_site;
+int vfm_pack_weights(const vfm_pack_site* table_dev, int nsites, long max_tiles, int dt, void* stream);
+
 /* ---- launch plans -------------------------------------------------------------------------------------- */
 /* A recorded sequence of the calls above, replayed in order on one stream by ONE call.  The hot path's backbone is a fixed launch
  * sequence per step (18 launches per transformer block: rein/models/backbones/dino_v2.py:259-291 forward_features and its backward) over

@@ -10,6 +10,9 @@ The nn.Modules below are *parameter containers* that reproduce the reference's s
                   the rank-32 path costs no extra pass over the activations (peft lora.Linear semantics,
                   lora_backbone.py:16-23; scaling alpha/r).
   backward      : hand-written (frozen base => only activation gradients + LoRA A/B weight gradients).
+  full training : a bare DinoVisionTransformer in train() mode trains every base weight that enters the graph
+                  (DinoEngine._backward_full: the weight / bias / LayerNorm / LayerScale / embedding gradients on top of the
+                  activation gradients).
 """
 import math
 
@@ -121,8 +124,29 @@ class DinoVisionTransformer(nn.Module):
             [_Block(embed_dim, num_heads, mlp_ratio, qkv_bias, proj_bias, ffn_bias, init_values) for _ in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)  # present in checkpoints, NOT applied to the taps (dino_v2.py:252-268)
         self.mask_token = nn.Parameter(torch.zeros(1, embed_dim))
+        self.drop_path_rate = float(drop_path_rate)
+        self._full_train = False
         self._engine = None
         self.register_load_state_dict_post_hook(lambda m, keys: m.engine().invalidate())
+
+    def inert_params(self):
+        """Parameters of the checkpoint that never enter the graph: the final norm is not applied to the taps and nothing is masked."""
+        return list(self.norm.parameters()) + [self.mask_token]
+
+    def train(self, mode=True):
+        """A bare backbone (no LoRA wrapper, no adapter) in train mode is fine-tuned whole.  torch's AdamW skips grad-less parameters, the
+        flat-buffer optimiser would weight-decay them: `norm.*` and `mask_token` are frozen here (and stay in the checkpoint), as the inert
+        EVA02 adapters are in LoRABackbone.train."""
+        super().train(mode)
+        self._full_train = bool(mode)
+        if mode and self.engine().bare():
+            for p in self.inert_params():
+                p.requires_grad = False
+        return self
+
+    def full_training(self):
+        """Is the base being trained?  (next to adapter_training(): what EncoderDecoder._tokens passes to forward_tokens)"""
+        return self._full_train and self.engine().bare() and self.patch_embed.proj.weight.requires_grad
 
     def engine(self):
         if self._engine is None:
@@ -259,6 +283,9 @@ class ReinsDinoVisionTransformer(DinoVisionTransformer):
     def adapter_training(self):
         return self._rein_train
 
+    def full_training(self):
+        return False
+
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
         """reins_dinov2.py:42-49: only the keys that contain 'rein' are kept (the frozen base comes from its own checkpoint)."""
         if args:   # torch's deprecated positional form (destination, prefix, keep_vars)
@@ -367,6 +394,15 @@ class Packed:
         if is_half(cd):
             self.wt = ops.empty_ld(k_pad, n, cd, w_f32.device, zero=True)
             ops.transpose(w_f32, self.wt[:k], pad_rows=n)
+
+    @classmethod
+    def alias(cls, w_f32):
+        """f32 mode, a TRAINED weight: the operand the GEMMs read IS the optimiser's master (no copy to refresh after a step)."""
+        assert w_f32.dtype == torch.float32 and w_f32.dim() == 2 and w_f32.is_contiguous()
+        self = cls.__new__(cls)
+        self.n, self.k = w_f32.shape
+        self.w, self.wt = w_f32, None
+        return self
 
     def fwd(self, a, out, **epi):
         return ops.gemm(a, self.w, out, **epi)
@@ -554,8 +590,43 @@ class DinoEngine:
     def rein_on(self):
         return getattr(self.vit, "reins", None) is not None
 
+    def bare(self):
+        return not self.lora_on() and not self.rein_on()
+
+    def full_on(self):
+        return self.bare() and getattr(self.vit, "full_training", lambda: False)()
+
+    def full_params(self):
+        """The base parameters that enter the graph, in the fixed order _backward_full hands their gradients back: the embeddings, then per
+        block norm1, qkv, proj, ls1, norm2, fc1, fc2, ls2 (absent biases are left out)."""
+        v = self.vit
+        out = [v.patch_embed.proj.weight, v.patch_embed.proj.bias, v.cls_token, v.pos_embed]
+        for blk in v.blocks:
+            out += [blk.norm1.weight, blk.norm1.bias, blk.attn.qkv.weight, blk.attn.qkv.bias, blk.attn.proj.weight, blk.attn.proj.bias,
+                    blk.ls1.gamma, blk.norm2.weight, blk.norm2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight,
+                    blk.mlp.fc2.bias, blk.ls2.gamma]
+        return [p for p in out if p is not None]
+
+    def check_full_training(self, hp, wp):
+        """What full fine-tuning refuses, by the option's name (no GPU needed to ask)."""
+        from .precision import split3 as _x3_mode
+        v = self.vit
+        if v.drop_path_rate > 0:
+            raise NotImplementedError(f"drop_path_rate={v.drop_path_rate}: stochastic depth is not on the HIP training path; full fine-tuning "
+                                      "of DinoVisionTransformer needs drop_path_rate=0")
+        if _x3_mode():
+            raise NotImplementedError("precision mode 'bf16x3' is a prediction mode: full fine-tuning of DinoVisionTransformer runs in "
+                                      "f32, bf16 or fp16")
+        s = int(math.sqrt(v.pos_embed.shape[1] - 1))
+        if (hp, wp) != (s, s):
+            raise NotImplementedError(f"img_size={v.img_size}: the training token grid {hp}x{wp} differs from the pos_embed grid {s}x{s}; "
+                                      "the pos_embed gradient would have to pass back through the bicubic interpolation - train crops of "
+                                      "img_size (the reference trains 512x512 crops at img_size=512)")
+
     def trainable(self):
         out = []
+        if self.full_on():
+            return self.full_params()
         if self.lora_on():
             for blk in self.vit.blocks:
                 out += [blk.attn.qkv.lora_A["default"].weight, blk.attn.qkv.lora_B["default"].weight]
@@ -567,11 +638,27 @@ class DinoEngine:
     def packed(self):
         cd = compute_dtype()
         dev = self.vit.pos_embed.device
-        if self._packed is not None and self._packed["cd"] == cd and self._packed["dev"] == dev:
-            return self._packed
         v = self.vit
+        # a TRAINED base (bare backbone whose weights require gradients): the fp32 vectors alias the master, the packed 2-D images are
+        # rewritten after every optimiser step (one launch: ops.PackTable), keyed on PARAM_EPOCH like the decoder heads' pack cache
+        tb = self.bare() and v.patch_embed.proj.weight.requires_grad
+        P = self._packed
+        if P is not None and P["cd"] == cd and P["dev"] == dev and P.get("trained", False) == tb:
+            if not tb:
+                return P
+            if P["ptrs"] == [p.data_ptr() for p in self.full_params()]:
+                from .optim import PARAM_EPOCH
+                key = (PARAM_EPOCH[0], sum(p._version for p in P["params"]))
+                if P["epoch"] != key:
+                    if P["pack_table"] is not None:
+                        P["pack_table"].run()
+                    P["epoch"] = key
+                    self._pos_cache = {}    # (position embeddings interpolated to other grids: the embedding moved)
+                return P
         D = v.embed_dim
-        P = dict(cd=cd, dev=dev, layers=[])
+        P = dict(cd=cd, dev=dev, layers=[], trained=tb)
+        if tb:
+            return self._pack_trained(P)
         with torch.no_grad():
             pw = v.patch_embed.proj.weight.detach().reshape(D, -1)
             P["pe"] = Packed(pw, cd)
@@ -598,6 +685,47 @@ class DinoEngine:
                     Lp["a"] = torch.zeros(R_PAD, D, dtype=cd, device=dev)       # A padded to 64 rows   [r, in]
                     Lp["at"] = torch.zeros(D, R_PAD, dtype=cd, device=dev)      # A^T                   [in, r]
                 P["layers"].append(Lp)
+        self._packed = P
+        return P
+
+    def _pack_trained(self, P):
+        """packed() of a trained base.  Every fp32 vector (biases, LayerNorm / LayerScale weights, cls, pos) IS the parameter's storage - the
+        optimiser's flat master once FusedAdamW has re-pointed it - and so is, in the f32 mode, every 2-D GEMM operand (Packed.alias).  In
+        the 16-bit modes the 2-D images are Packed(...) as for a frozen base, and P["pack_table"] rewrites all of them from the master in
+        one launch: the same conversions, hence the same bits, as building them afresh."""
+        from .optim import PARAM_EPOCH
+        v = self.vit
+        cd, D = P["cd"], v.embed_dim
+        params = self.full_params()
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise TypeError("full fine-tuning needs contiguous fp32 backbone parameters (the packed operands alias or follow them)")
+        sites = []
+
+        def pack(w):
+            w = w.detach()
+            w2 = w.reshape(w.shape[0], -1)
+            if cd == torch.float32:
+                return Packed.alias(w2)
+            pk = Packed(w2, cd)
+            sites.append((w2, pk.w, pk.wt))
+            return pk
+
+        vec = lambda p: None if p is None else p.detach().reshape(-1)   # noqa: E731
+        with torch.no_grad():
+            P["pe"] = pack(v.patch_embed.proj.weight)
+            P["pe_b"] = vec(v.patch_embed.proj.bias)
+            P["cls"] = vec(v.cls_token)
+            for blk in v.blocks:
+                P["layers"].append(dict(
+                    qkv=pack(blk.attn.qkv.weight), qkv_b=vec(blk.attn.qkv.bias), proj=pack(blk.attn.proj.weight), proj_b=vec(blk.attn.proj.bias),
+                    fc1=pack(blk.mlp.fc1.weight), fc1_b=vec(blk.mlp.fc1.bias), fc2=pack(blk.mlp.fc2.weight), fc2_b=vec(blk.mlp.fc2.bias),
+                    g1=vec(blk.ls1.gamma), g2=vec(blk.ls2.gamma), n1w=vec(blk.norm1.weight), n1b=vec(blk.norm1.bias),
+                    n2w=vec(blk.norm2.weight), n2b=vec(blk.norm2.bias)))
+        P["ptrs"] = [p.data_ptr() for p in params]
+        P["params"] = params
+        P["pack_table"] = ops.PackTable(sites) if sites else None
+        P["epoch"] = (PARAM_EPOCH[0], sum(p._version for p in params))
         self._packed = P
         return P
 
@@ -683,6 +811,9 @@ class DinoEngine:
         hp, wp = sizes[0]
         assert all(s == (hp, wp) for s in sizes), "all jobs of one backbone call must share the token grid"
         Np = hp * wp
+        full = bool(training and need_grad and self.full_on())   # the base itself is trained: keep what its weight gradients read
+        if full:
+            self.check_full_training(hp, wp)
         nimg = sum(j[0].shape[0] for j in jobs)
         Mp, M = nimg * Np, nimg * Np + nimg
         kpe = 3 * ps * ps
@@ -697,7 +828,9 @@ class DinoEngine:
         plan = self._train_plan(P, nimg, Np, training, merged) if need_grad else None
         x = plan.X[0] if plan is not None else torch.empty(M, D, dtype=torch.float32, device=dev)
         ops.assemble_tokens(ptok, P["cls"], self.pos_tokens(hp, wp), x, nimg, Np, D)
-        del ptok, A0
+        del ptok
+        if not full:
+            del A0    # (full fine-tuning: the patch rows are the patch embedding's weight-gradient operand)
         nt = len(v.out_indices)
         from .precision import eval_heads_fp32
         tap_dt = torch.float32 if (not training and not need_grad and eval_heads_fp32()) else cd
@@ -759,21 +892,25 @@ class DinoEngine:
             so = "only" if (x3 and not training and not need_grad) else None
             ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, lse, nimg, H, hd, Np, 1, Np, 1, scale, keep_split=training, o_split=so)
             xm = torch.empty(M, D, dtype=torch.float32, device=dev)
-            Lp["proj"].fwd(ao, xm, bias=Lp["proj_b"], colscale=Lp["g1"], residual=x)
+            # full fine-tuning: the epilogue's second output is the branch output BEFORE the LayerScale column scale (bias included) -
+            # what d gamma reads; x_mid / x_out themselves are what every other caller gets
+            u1 = torch.empty(M, D, dtype=cd, device=dev) if full else None
+            u2 = torch.empty(M, D, dtype=cd, device=dev) if full else None
+            Lp["proj"].fwd(ao, xm, bias=Lp["proj_b"], colscale=Lp["g1"], residual=x, **({"c2": u1} if full else {}))
             a2 = torch.empty(M, D, dtype=cd, device=dev)
             st2 = torch.empty(M, 2, dtype=torch.float32, device=dev)
             ops.layernorm_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2, split_out=so)
             hid = Lp["fc1"].n
             g = ops.empty_ld(M, hid, cd, dev)
-            if training and (lora or (rein is not None and need_grad)):   # the forward also saves gelu'(pre-activation): what fc2's dgrad multiplies by (mlp.py:34-40)
+            if training and (lora or (rein is not None and need_grad) or full):   # the forward also saves gelu'(pre-activation): what fc2's dgrad multiplies by (mlp.py:34-40)
                 hpre = torch.empty(M, hid, dtype=cd, device=dev)
                 Lp["fc1"].fwd(a2, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU_DGELU, c2=hpre)
             else:
                 hpre = None
                 Lp["fc1"].fwd(a2, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU, **({"c_split": so} if so else {}))
             xo = torch.empty(M, D, dtype=torch.float32, device=dev)
-            Lp["fc2"].fwd(g, xo, bias=Lp["fc2_b"], colscale=Lp["g2"], residual=xm)
-            S.update(a1=a1, st1=st1, qkv=qkv, ao=ao, lse=lse, x_mid=xm, a2=a2, st2=st2, hpre=hpre, g=g)
+            Lp["fc2"].fwd(g, xo, bias=Lp["fc2_b"], colscale=Lp["g2"], residual=xm, **({"c2": u2} if full else {}))
+            S.update(a1=a1, st1=st1, qkv=qkv, ao=ao, lse=lse, x_mid=xm, a2=a2, st2=st2, hpre=hpre, g=g, u1=u1, u2=u2)
             saved.append(S)
             x = xo
             if rein is not None:   # the adapter step on the patch rows; the taps below read its output (reins_dinov2.py:22-33)
@@ -781,7 +918,8 @@ class DinoEngine:
             for i, oi in enumerate(v.out_indices):   # (an index may be listed more than once: every copy is a tap of its own)
                 if oi == li:
                     ops.cast(x[:Mp], xcat[:, i * D:(i + 1) * D])
-        ctx = dict(saved=saved, nimg=nimg, Np=Np, M=M, Mp=Mp, P=P, training=training, A1all=A1all, XDall=XDall, rein=rein)
+        ctx = dict(saved=saved, nimg=nimg, Np=Np, M=M, Mp=Mp, P=P, training=training, A1all=A1all, XDall=XDall, rein=rein,
+                   full=full, A0=A0 if full else None)
         return xcat, (hp, wp), ctx
 
     def _train_plan(self, P, nimg, Np, training, merged):
@@ -812,6 +950,8 @@ class DinoEngine:
             finally:
                 plan.busy = False
             return [None] * (2 * len(self.vit.blocks))
+        if ctx.get("full"):
+            return self._backward_full(ctx, dxcat)
         v, P = self.vit, ctx["P"]
         cd, dev = P["cd"], P["dev"]
         D, H = v.embed_dim, v.num_heads
@@ -934,6 +1074,122 @@ class DinoEngine:
         if rein is not None:
             grads += self._rein_backward_end(rein, rein_acc)
         return grads
+
+    # ---- full fine-tuning: d(xcat) -> gradients of full_params(), in that order (None where they went into the flat buffer)
+    @staticmethod
+    def _wgrad_full(dy, x, out):
+        """out[N, K] += dy^T @ x over the token rows (dy [M, N], x [M, K] token-major, consumed in place; `out` a contiguous fp32 view -
+        the parameter's slice of the optimiser's flat gradient buffer).  16-bit: the transposed-operand MFMA GEMM (GEMM_ATBT) with the
+        accumulation in its epilogue; VFMSEG_FULL_WGRAD_SPLITK = k > 1 cuts the token reduction into k slabs (gemm_splitk_tn) that meet in
+        a fixed order (slab_reduce) - more blocks for the 64-tile gradients, one more pass over k fp32 images.
+        f32: strided operands.  Deterministic either way."""
+        M, N = dy.shape
+        K = x.shape[1]
+        if not is_half(dy.dtype):
+            ops.gemm(dy, x, out, residual=out, trans_a=True, trans_b=True)
+            return
+        if N % 8 or K % 8:
+            wgrad(dy, x, out)      # (a patch size whose 3 P^2 is no multiple of 8: explicit transposes)
+            return
+        kch = int(os.environ.get("VFMSEG_FULL_WGRAD_SPLITK", "1"))
+        steps = (M + 63) // 64
+        if kch > 1 and steps % kch == 0 and dy.data_ptr() % 16 == 0 and dy.stride(0) % 8 == 0:
+            slabs = torch.empty(kch, N, K, dtype=torch.float32, device=dy.device)
+            ops.gemm_splitk_tn(dy, x, slabs, kch)
+            ops.slab_reduce(slabs, N, out, K, 1, accumulate=True)
+            return
+        ops.gemm_tn_batched(dy.unsqueeze(0), x.unsqueeze(0), out.unsqueeze(0), M, accumulate=True)
+
+    def _backward_full(self, ctx, dxcat):
+        """The block backward of backward() plus every parameter gradient of the base: per block, last to first,
+            dW_fc2 += t^T g, (d ls2.gamma, db_fc2, t = cd(dx g2)) from ONE pass (ops.branch_param_grads), dW_fc1 += dh^T a2, db_fc1,
+            LayerNorm-2 dw / db, dW_proj += t^T ao, (d ls1.gamma, db_proj, t), dW_qkv += dqkv^T a1, db_qkv, LayerNorm-1 dw / db,
+        then d pos_embed (token-row gradients summed over the images, class row included), d cls_token, dW_pe = dptok^T A0, db_pe.
+        Gradients accumulate straight into the optimiser's flat buffer where there is one.  block_done(li) fires when block li's
+        gradients are final, i.e. after its LayerNorm-1 backward."""
+        from .functional import direct_grad_target
+        v, P = self.vit, ctx["P"]
+        cd, dev = P["cd"], P["dev"]
+        D, H = v.embed_dim, v.num_heads
+        hd = D // H
+        scale = hd ** -0.5
+        M, Mp, nimg, Np = ctx["M"], ctx["Mp"], ctx["nimg"], ctx["Np"]
+        params = self.full_params()
+        tgt, ret = {}, {}
+
+        def G(p):
+            """fp32 accumulator of p's gradient, flat: the flat-buffer slice, or a zeroed tensor that is handed to autograd"""
+            if p is None:
+                return None
+            k = id(p)
+            if k not in tgt:
+                t_ = direct_grad_target(p)
+                if t_ is None:
+                    t_ = ret[k] = torch.zeros(p.shape, dtype=torch.float32, device=dev)
+                tgt[k] = t_
+            return tgt[k].view(-1)
+
+        def G2(p):
+            return G(p).view(p.shape[0], -1)
+
+        dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
+        t = torch.empty(M, D, dtype=cd, device=dev)
+        for li in range(len(v.blocks) - 1, -1, -1):
+            blk, Lp, S = v.blocks[li], P["layers"][li], ctx["saved"][li]
+            for i, oi in enumerate(v.out_indices):   # dx is d(x_out) of this block: its tap gradients go in first
+                if oi == li:
+                    src = dxcat[:, i * D:(i + 1) * D]
+                    ops.strided_copy(src, dx, (Mp, D), (src.stride(0), 1), (D, 1), accumulate=True)
+            # ---- MLP branch: x_out = x_mid + g2 * (fc2(gelu(fc1(LN2(x_mid)))) + b)
+            fc1, fc2 = blk.mlp.fc1, blk.mlp.fc2
+            ops.branch_param_grads(dx, S["u2"], Lp["g2"], dgamma=G(blk.ls2.gamma), dbias=G(fc2.bias), t=t, accumulate=True)
+            self._wgrad_full(t, S["g"], G2(fc2.weight))
+            hid = Lp["fc1"].n
+            dh = ops.empty_ld(M, hid, cd, dev)
+            Lp["fc2"].dgrad(t, dh, ep_mode=ops.EP_MUL, aux=S["hpre"])
+            self._wgrad_full(dh, S["a2"], G2(fc1.weight))
+            if fc1.bias is not None:
+                ops.colsum(dh, G(fc1.bias), accumulate=True)
+            dn = torch.empty(M, D, dtype=cd, device=dev)
+            Lp["fc1"].dgrad(dh, dn)
+            del dh
+            ops.layernorm_bwd(dn, S["x_mid"], Lp["n2w"], S["st2"], dx, accumulate_dx=True, dw=G(blk.norm2.weight), db=G(blk.norm2.bias))
+            # ---- attention branch: x_mid = x_in + g1 * (proj(attn(qkv(LN1(x_in)))) + b)
+            qkv_l, proj = blk.attn.qkv, blk.attn.proj
+            ops.branch_param_grads(dx, S["u1"], Lp["g1"], dgamma=G(blk.ls1.gamma), dbias=G(proj.bias), t=t, accumulate=True)
+            self._wgrad_full(t, S["ao"], G2(proj.weight))
+            dao = dn
+            Lp["proj"].dgrad(t, dao)
+            dqkv = torch.empty(M, 3 * D, dtype=cd, device=dev)
+            qkv = S["qkv"]
+            ops.attn_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], S["ao"], S["lse"], dao, dqkv[:, :D], dqkv[:, D:2 * D],
+                         dqkv[:, 2 * D:], nimg, H, hd, Np, 1, Np, 1, scale)
+            self._wgrad_full(dqkv, S["a1"], G2(qkv_l.weight))
+            if qkv_l.bias is not None:
+                ops.colsum(dqkv, G(qkv_l.bias), accumulate=True)
+            da1 = torch.empty(M, D, dtype=cd, device=dev)
+            Lp["qkv"].dgrad(dqkv, da1)
+            ops.layernorm_bwd(da1, S["x_in"], Lp["n1w"], S["st1"], dx, accumulate_dx=True, dw=G(blk.norm1.weight), db=G(blk.norm1.bias))
+            ctx["saved"][li] = None
+            if BACKWARD_EVENTS["block_done"] is not None:
+                BACKWARD_EVENTS["block_done"](li)
+        # ---- embeddings: x0[patch j of image i] = ptok + pos[1 + j], x0[class row i] = cls + pos[0]
+        gpos = G(v.pos_embed).view(Np + 1, D)
+        for i in range(nimg):
+            ops.strided_copy(dx[i * Np:(i + 1) * Np], gpos[1:], (Np, D), (D, 1), (D, 1), accumulate=True)
+        ops.colsum(dx[Mp:], gpos[0], accumulate=True)
+        ops.colsum(dx[Mp:], G(v.cls_token), accumulate=True)
+        pe = v.patch_embed.proj
+        if pe.bias is not None:
+            ops.colsum(dx[:Mp], G(pe.bias), accumulate=True)
+        if cd == torch.float32:
+            dptok = dx[:Mp]
+        else:
+            dptok = torch.empty(Mp, D, dtype=cd, device=dev)
+            ops.cast(dx[:Mp], dptok)
+        self._wgrad_full(dptok, ctx["A0"], G2(pe.weight))
+        ctx["A0"] = None
+        return [ret.get(id(p)) for p in params]
 
     # ---- Rein adapter (reins.py:84-116): x' = x + scale * mlp_delta_f(softmax(c x T^T)[:, 1:] V + x) on the patch rows
     def _rein_fused(self, P):

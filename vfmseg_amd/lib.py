@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvfmseg_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvfmseg_hip_f16.so")
 
 F32, BF16, U8, I64, SPLIT3 = 0, 1, 2, 3, 4
-ABI_VERSION = 11   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax, 8 vfm_augment_u8, 9 the loss options (vfm_ohem_prob, vfm_ohem_threshold, vfm_label_weight), 10 gradient clipping (vfm_grad_norm, vfm_adamw_clip), 11 the Dice loss (vfm_upsample_dice_sums, vfm_dice_finish, vfm_upsample_dice_bwd): an older one lacks the symbols
+ABI_VERSION = 12   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax, 8 vfm_augment_u8, 9 the loss options (vfm_ohem_prob, vfm_ohem_threshold, vfm_label_weight), 10 gradient clipping (vfm_grad_norm, vfm_adamw_clip), 11 the Dice loss (vfm_upsample_dice_sums, vfm_dice_finish, vfm_upsample_dice_bwd), 12 full fine-tuning (vfm_branch_param_grads, vfm_pack_weights): an older one lacks the symbols
 EP_NONE, EP_GELU, EP_RELU, EP_MUL_GELU_GRAD, EP_MUL, EP_QGELU, EP_MUL_QGELU_GRAD, EP_GELU_DGELU = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_QGELU = 0, 1, 2, 3
 
@@ -195,6 +195,8 @@ SIGNATURES = {
     "vfm_amp_update": [vp, vp, cf, cf, ci, ci, vp],
     "vfm_grad_norm": [vp, cl, ci, cf, cf, vp, vp, vp, vp, vp],
     "vfm_adamw_clip": [vp, vp, vp, vp, cl, vp, vp, vp, ci, cf, cf, cf, cf, ci, cf, ci, ci, vp, vp, vp, cf, vp],
+    "vfm_branch_param_grads": [vp, cl, vp, ci, cl, vp, cl, cl, vp, vp, ci, vp, ci, cl, vp, vp],
+    "vfm_pack_weights": [vp, ci, cl, ci, vp],
     "vfm_run_plan": [C.POINTER(PlanOp), ci, u64, u64, vp],
     "vfm_prof_config": [ci],
     "vfm_prof_read": [C.POINTER(C.c_double), ci],

@@ -632,6 +632,61 @@ class LoraPackTable:
         L.check(lib.vfm_lora_pack(L.ptr(self.table), self.n, self.max_elems, self.dt, L.stream()), "vfm_lora_pack")
 
 
+BRANCH_WS_PARTS = 128   # VFM_BRANCH_WS_PARTS
+
+
+def branch_param_grads(dx, u, gamma, dgamma=None, dbias=None, t=None, accumulate=False):
+    """Residual branch x_out = x_in + gamma * (y W^T + b), one read pass over dx (fp32 [M, D]) and the saved pre-scale output u
+    (fp32 | half [M, D]):  dgamma[c] (+)= sum_m dx u,  dbias[c] (+)= gamma[c] sum_m dx,  t = cast(dx * gamma) - the dgrad operand, the
+    bits ops.cast(dx, t, gamma) writes.  Each output may be None (u may be None when dgamma is).  Deterministic, no atomics."""
+    lib = L.load()
+    M, D = dx.shape
+    assert dx.dtype == torch.float32 and gamma.dtype == torch.float32 and gamma.is_contiguous() and gamma.numel() == D
+    for o in (dgamma, dbias):
+        assert o is None or (o.dtype == torch.float32 and o.is_contiguous() and o.numel() == D)
+    assert u is None or tuple(u.shape) == (M, D)
+    assert t is None or tuple(t.shape) == (M, D)
+    ws = workspace(2 * BRANCH_WS_PARTS * D, dx.device, "branch")
+    L.check(lib.vfm_branch_param_grads(L.ptr(dx), _ld(dx), L.ptr(u), L.dt_of(u) if u is not None else 0, _ld(u) if u is not None else 0,
+                                       L.ptr(gamma), M, D, L.ptr(dgamma), L.ptr(dbias), int(accumulate), L.ptr(t),
+                                       L.dt_of(t) if t is not None else 0, _ld(t) if t is not None else 0, L.ptr(ws), L.stream()),
+            "vfm_branch_param_grads")
+    return t
+
+
+class PackTable:
+    """Device-resident table for vfm_pack_weights: sites = [(src fp32 [N, K] contiguous, w [N, >=K], wt [K, >=N] or None)] - the fp32
+    master of a trained 2-D weight and the packed GEMM operands it feeds.  Built once per packing (the master lives in the optimiser's
+    flat buffer, the images in the engine's packed dict: stable pointers); run() rewrites every image with one launch."""
+
+    def __init__(self, sites):
+        import struct
+        buf = bytearray()
+        self.keep, self.max_tiles, self.n = [], 0, len(sites)
+        self.dt = None
+        for src, w, wt in sites:
+            n, k = src.shape
+            assert src.dtype == torch.float32 and src.is_contiguous() and src.is_cuda and w.shape[0] == n and w.shape[1] >= k and w.stride(1) == 1
+            assert wt is None or (wt.dtype == w.dtype and wt.shape[0] >= k and wt.shape[1] >= n and wt.stride(1) == 1)
+            assert self.dt in (None, w.dtype), "one table packs into one dtype"
+            self.dt = w.dtype
+            buf += struct.pack("3Q4q", src.data_ptr(), w.data_ptr(), wt.data_ptr() if wt is not None else 0, n, k, w.stride(0),
+                               wt.stride(0) if wt is not None else 0)
+            self.keep += [src, w, wt]
+            self.max_tiles = max(self.max_tiles, ((n + 63) // 64) * ((k + 63) // 64))
+        self.ptrs = [s_[0].data_ptr() for s_ in sites]
+        self.table = torch.frombuffer(buf, dtype=torch.uint8).clone().to(sites[0][0].device) if sites else None
+
+    def valid_for(self, srcs):
+        return self.ptrs == [s_.data_ptr() for s_ in srcs]
+
+    def run(self):
+        if self.n:
+            lib = L.load()
+            L.check(lib.vfm_pack_weights(L.ptr(self.table), self.n, self.max_tiles, L.dt_of(self.keep[1]), L.stream()),
+                    "vfm_pack_weights")
+
+
 def slab_reduce(slabs, rows_used, dst, sp, sq, alpha=1.0, accumulate=False):
     """dst[p*sp + q*sq] (+)= alpha * sum_k slabs[k, p, q] for p < rows_used (slabs fp32 [kch, P, Q], dst fp32)."""
     lib = L.load()

@@ -63,15 +63,34 @@ def grad_group(n):
     """Which bucket family a parameter's gradient belongs to (see production_order)."""
     if is_rein_name(n):
         return "reins"
-    return "lora" if "lora_" in n else ("aux_decoder" if n.startswith("aux_decoder") else "decode_head")
+    if "lora_" in n:
+        return "lora"
+    if n.startswith("backbone."):    # a trained base weight (full fine-tuning): final only when its block's backward has run
+        return "backbone"
+    return "aux_decoder" if n.startswith("aux_decoder") else "decode_head"
+
+
+def backbone_block(n):
+    """Block index of a base weight's name (`backbone.blocks.N....`), or None for the embeddings (patch_embed / pos_embed / cls_token)."""
+    if ".blocks." not in n and not n.startswith("blocks."):
+        return None
+    try:
+        return int(n.split("blocks.")[1].split(".")[0])
+    except Exception:
+        return None
 
 
 def production_order(names):
     """Gradient-production order of backward: aux_decoder, decode_head, then LoRA blocks from the last to the first, then the Rein adapter
-    (`backbone.reins.*`: weights shared by all layers, whose gradients are complete only when the backbone backward ends)."""
+    (`backbone.reins.*`: weights shared by all layers, whose gradients are complete only when the backbone backward ends).  The base
+    weights of a fully fine-tuned backbone (`backbone.*`, neither LoRA nor Rein) follow the heads the same way: blocks from the last to
+    the first, then the embeddings, whose gradients are the last thing the backbone backward writes."""
     def key(n):
         if is_rein_name(n):
             return (3, 0, n)
+        if grad_group(n) == "backbone":
+            blk = backbone_block(n)
+            return (4, 1, n) if blk is None else (4, -blk, n)
         if "lora_" in n:
             try:
                 blk = int(n.split("blocks.")[1].split(".")[0])

@@ -52,10 +52,20 @@ def broadcast_params(model, src=0):
         dist.broadcast(t.data, src)
 
 
-def make_buckets(names, offsets, max_lora_buckets=2):
+# Full fine-tuning: the base weights of DINOv2-L are ~304 M fp32 gradients (1.2 GB), seventy times what the heads and adapters send.
+# One bucket would leave nothing to overlap (it is final only when the backward ends); one per block would be 24 collectives whose
+# launch and synchronisation cost adds up on a point-to-point fabric where few large transfers beat many small ones (above).  Four
+# buckets of whole blocks: three quarters of the traffic leaves while later blocks' backward still runs, each transfer (~300 MB) stays
+# far above the size where the collective reaches its bandwidth, and the tail that nothing can hide is one quarter.
+MAX_BACKBONE_BUCKETS = 4
+
+
+def make_buckets(names, offsets, max_lora_buckets=2, max_backbone_buckets=MAX_BACKBONE_BUCKETS):
     """Contiguous [start, end) slices of the flat gradient buffer in production order.
-    names/offsets as in FusedAdamW (offsets has len(names)+1 entries)."""
-    from .optim import grad_group
+    names/offsets as in FusedAdamW (offsets has len(names)+1 entries).
+    The `backbone` family (full fine-tuning) is cut into at most max_backbone_buckets slices `backbone0`, `backbone1`, ... of whole
+    blocks, roughly equal in size, last blocks first; the embeddings ride in the last one."""
+    from .optim import backbone_block, grad_group
     groups = []
     cur = None
     for i, nm in enumerate(names):
@@ -80,6 +90,27 @@ def make_buckets(names, offsets, max_lora_buckets=2):
                     k += 1
             if start < b:
                 out.append((f"lora{k - 1}", start, b))
+        elif g == "backbone":
+            idx = [i for i, nm in enumerate(names) if grad_group(nm) == "backbone"]
+            blocks = sorted({backbone_block(names[i]) for i in idx} - {None}, reverse=True)
+            nb = max(1, min(max_backbone_buckets, len(blocks)))
+            # the blocks are equal in size: bucket k gets len(blocks) // nb of them (the first len(blocks) % nb buckets one more)
+            quota = [len(blocks) // nb + (1 if k < len(blocks) % nb else 0) for k in range(nb)]
+            ends = set()      # the block that completes each bucket but the last
+            done = 0
+            for q in quota[:-1]:
+                done += q
+                ends.add(blocks[done - 1])
+            start, k = a, 0
+            for j, i in enumerate(idx):
+                # a cut falls only where the next parameter belongs to another block
+                nxt = idx[j + 1] if j + 1 < len(idx) else None
+                blk = backbone_block(names[i])
+                if nxt is not None and blk in ends and backbone_block(names[nxt]) != blk:
+                    out.append((f"backbone{k}", start, offsets[i + 1]))
+                    start = offsets[i + 1]
+                    k += 1
+            out.append((f"backbone{k}", start, b))
         else:
             out.append((g, a, b))
     return out
@@ -175,7 +206,8 @@ def attach(model, optim_wrapper, group=None):
     gs = GradSync(opt.gflat, buckets, group)
     optim_wrapper.grad_sync = gs
     from . import backbones
-    head_ids = [i for i, b in enumerate(buckets) if not b[0].startswith("lora") and b[0] != "reins"]
+    bb_ids = [i for i, b in enumerate(buckets) if b[0].startswith("backbone")]   # base weights of a fully fine-tuned backbone
+    head_ids = [i for i, b in enumerate(buckets) if not b[0].startswith("lora") and b[0] != "reins" and i not in bb_ids]
     rein_ids = [i for i, b in enumerate(buckets) if b[0] == "reins"]   # shared by all layers: final when the backbone backward ends
     lora_ids = [i for i, b in enumerate(buckets) if b[0].startswith("lora")]
     # block index whose completion finalises LoRA bucket k: the smallest block number among the parameters it holds
@@ -184,6 +216,13 @@ def attach(model, optim_wrapper, group=None):
         _, a, b = buckets[i]
         blks = [int(nm.split("blocks.")[1].split(".")[0]) for nm, o in zip(opt.names, opt.offsets[:-1]) if a <= o < b and "lora_" in nm]
         last_block[min(blks)] = i
+    # the same for the base-weight buckets, except the last one: it holds the embeddings, whose gradients the backward writes last
+    from .optim import backbone_block
+    for i in bb_ids[:-1]:
+        _, a, b = buckets[i]
+        blks = [backbone_block(nm) for nm, o in zip(opt.names, opt.offsets[:-1]) if a <= o < b]
+        last_block[min(x for x in blks if x is not None)] = i
+    rein_ids = rein_ids + bb_ids[-1:]
 
     def heads_done():
         for i in head_ids:

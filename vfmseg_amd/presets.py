@@ -244,6 +244,30 @@ def frozen_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=N
     )
 
 
+def full_dinov2_linear(depth=24, embed_dim=1024, num_heads=16, checkpoint=None, img_size=512):
+    """Full fine-tuning, the "Full" row of the PEFT comparisons: mmseg's plain `EncoderDecoder` over a bare `DinoVisionTransformer` (every
+    backbone weight that enters the graph trains) with the LinearHead of dinov2_linear().  `checkpoint` (the
+    converted DINOv2 weights, bare keys) goes into the backbone's init_cfg, as in frozen_dinov2_segformer()."""
+    bb = dinov2_backbone(depth, embed_dim, num_heads, img_size)
+    bb["init_cfg"] = dict(type="Pretrained", checkpoint=checkpoint)
+    return dict(
+        type="EncoderDecoder",
+        data_preprocessor=dict(_PREPROC, size=(img_size, img_size)),
+        backbone=bb,
+        decode_head=linear_head(embed_dim),
+        train_cfg=dict(),
+        test_cfg=dict(mode="whole"),
+    )
+
+
+def full_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=None, img_size=512):
+    """frozen_dinov2_segformer() with the backbone trained: EncoderDecoder, bare DINOv2-L, SegformerHead, 512 / 341 slide test."""
+    cfg = full_dinov2_linear(depth, embed_dim, num_heads, checkpoint, img_size)
+    cfg["decode_head"] = segformer_head(embed_dim)
+    cfg["test_cfg"] = dict(_SLIDE_341)
+    return cfg
+
+
 def uda_rein_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint=None, work_dir="work_dirs/tmp"):
     """configs/uda/uda_rein_dinov2_Segformer_512x512.py: DACS self-training around the Rein DINOv2-L + SegformerHead model.  The reference's
     values, except blur=False and color_jitter_probability=1.0: its colour-jitter / blur branches need kornia, whose import it has
@@ -266,9 +290,18 @@ def uda_rein_dinov2_segformer(depth=24, embed_dim=1024, num_heads=16, checkpoint
     return cfg
 
 
-def optim_cfg(clip_grad=None, accumulative_counts=1):
-    """clip_grad / accumulative_counts: mmengine OptimWrapper's keys (vfmseg_amd.optim.OptimWrapper); the defaults leave them out."""
+def optim_cfg(clip_grad=None, accumulative_counts=1, backbone_lr_mult=None):
+    """clip_grad / accumulative_counts: mmengine OptimWrapper's keys (vfmseg_amd.optim.OptimWrapper); the defaults leave them out.
+    backbone_lr_mult (full fine-tuning): adds custom_keys['backbone'] = dict(lr_mult=...) - mmseg's usual 0.1 for a pretrained backbone
+    under a fresh head.  The longest matching key wins (param_options) and 'backbone' is longer than 'norm': the LayerNorms of the blocks
+    would be decayed.  They are therefore named by keys that are longer still ('.norm1.weight', ...) and carry both the multiplier and
+    decay_mult=0."""
     embed_multi = dict(lr_mult=1.0, decay_mult=0.0)
+    bb_keys = {}
+    if backbone_lr_mult is not None:
+        bb_keys["backbone"] = dict(lr_mult=backbone_lr_mult)
+        for k in (".norm1.weight", ".norm1.bias", ".norm2.weight", ".norm2.bias"):
+            bb_keys[k] = dict(lr_mult=backbone_lr_mult, decay_mult=0.0)
     extra = {}
     if clip_grad is not None:
         extra["clip_grad"] = dict(clip_grad)
@@ -285,6 +318,7 @@ def optim_cfg(clip_grad=None, accumulative_counts=1):
                     "level_embed": embed_multi,
                     "learnable_tokens": embed_multi,
                     "reins.scale": embed_multi,
+                    **bb_keys,
                 },
                 norm_decay_mult=0.0,
             ),

@@ -168,6 +168,26 @@ class EncoderDecoder(nn.Module):
         self.out_channels = self.decode_head.out_channels
         self.train_cfg, self.test_cfg = CfgDict(train_cfg), CfgDict(test_cfg)
         self.with_neck = False
+        if type(self.backbone).__name__ == "DinoVisionTransformer":   # the bare backbone: its init_cfg is the pretrained base
+            self._load_backbone_init_cfg(backbone)
+
+    # full fine-tuning of a bare DinoVisionTransformer: the segmentors that send the backbone over several inputs per step or train it
+    # against a teacher (MsVFMEncoderDecoder, HRDAEncoderDecoder, DACS) refuse it by name
+    _full_finetune_ok = True
+
+    def _load_backbone_init_cfg(self, backbone):
+        """backbone init_cfg=dict(type='Pretrained', checkpoint=PATH | state dict) -> the backbone's weights, strictly: a file whose keys
+        do not match is an error, not an untrained base.  A backbone that reads its own init_cfg (ReinsDinoVisionTransformer) or has been
+        loaded already is left alone."""
+        ic = backbone.get("init_cfg") if isinstance(backbone, dict) else None
+        ck = ic.get("checkpoint") if isinstance(ic, dict) else None
+        if ck is not None and getattr(self.backbone, "pretrained", None) is None:
+            if ic.get("type", "Pretrained") != "Pretrained":
+                raise NotImplementedError(f"init_cfg type {ic.get('type')!r}: only dict(type='Pretrained', checkpoint=...) is read")
+            sd = torch.load(ck, map_location="cpu") if isinstance(ck, (str, os.PathLike)) else ck
+            sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+            self.backbone.load_state_dict(sd, strict=True)
+            self.backbone.pretrained = ck if isinstance(ck, (str, os.PathLike)) else "<state dict>"
 
     # ---- features
     def _tokens(self, jobs):
@@ -177,6 +197,15 @@ class EncoderDecoder(nn.Module):
                 xcat, (hp, wp) = bb.forward_tokens(jobs)
             elif hasattr(bb, "adapter_training"):   # a ViT that carries its own adapters (Rein) says whether they are being trained
                 xcat, (hp, wp) = bb.forward_tokens(jobs, training=bb.adapter_training())
+            elif getattr(bb, "full_training", None) is not None and bb.full_training() and torch.is_grad_enabled():
+                # a bare DinoVisionTransformer in train() mode: every base weight trains (full fine-tuning); eval() / no_grad calls stay
+                # on the prediction path below
+                if not self._full_finetune_ok:
+                    raise NotImplementedError(
+                        f"{type(self).__name__} over a bare DinoVisionTransformer in train() mode (full fine-tuning): only EncoderDecoder "
+                        "(whole / slide) trains the base; wrap the backbone (LoRABackbone, ReinsDinoVisionTransformer) or use the "
+                        "frozen-backbone segmentor")
+                xcat, (hp, wp) = bb.forward_tokens(jobs, training=True)
             else:
                 xcat, (hp, wp) = bb.forward_tokens(jobs, training=False)
             return xcat, hp, wp
@@ -469,14 +498,7 @@ class FrozenBackboneEncoderDecoder(EncoderDecoder):
         super().__init__(backbone=backbone, **kw)
         # dinov2_SegFormer_frozen.py: the frozen weights arrive through the backbone's init_cfg=dict(type="Pretrained", checkpoint=PATH);
         # a backbone that reads its own init_cfg (ReinsDinoVisionTransformer) has loaded them already
-        ic = backbone.get("init_cfg") if isinstance(backbone, dict) else None
-        ck = ic.get("checkpoint") if isinstance(ic, dict) else None
-        if ck is not None and getattr(self.backbone, "pretrained", None) is None:
-            if ic.get("type", "Pretrained") != "Pretrained":
-                raise NotImplementedError(f"init_cfg type {ic.get('type')!r}: only dict(type='Pretrained', checkpoint=...) is read")
-            sd = torch.load(ck, map_location="cpu") if isinstance(ck, (str, os.PathLike)) else ck
-            sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
-            self.backbone.load_state_dict(sd, strict=True)   # a file whose keys do not match is an error, not an untrained frozen base
+        self._load_backbone_init_cfg(backbone)   # a file whose keys do not match is an error, not an untrained frozen base
         self.train(self.training)   # frozen from construction on: an optimiser built before the first train() sees no backbone parameter
 
     def train(self, mode=True):
@@ -500,6 +522,8 @@ class FrozenBackboneEncoderDecoder(EncoderDecoder):
 
 @MODELS.register_module()
 class MsVFMEncoderDecoder(EncoderDecoder):
+    _full_finetune_ok = False   # a bare DinoVisionTransformer in train() mode is refused by name (EncoderDecoder._tokens)
+
     def __init__(self, backbone, decode_head, aux_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None,
                  pretrained=None, init_cfg=None, scales=[1], hr_crop_size=None, crop_coord_divisible=1, feature_scale=1,
                  data_preprocessor=None, debug=False, debug_interval=100, detail_loss=1.0):
@@ -721,6 +745,7 @@ class HRDAEncoderDecoder(EncoderDecoder):
     """rein/models/segmentors/hrda_encoder_decoder.py:62-447 (the HRDA multi-resolution baseline): the half-size image and a random
     full-resolution crop (training) or overlapping full-resolution crops (prediction) go through ONE backbone call; the HRDAHead fuses
     their logits by a learned scale attention."""
+    _full_finetune_ok = False   # a bare DinoVisionTransformer in train() mode is refused by name (EncoderDecoder._tokens)
 
     def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None, pretrained=None,
                  init_cfg=None, scales=[1], hr_crop_size=None, hr_slide_inference=True, hr_slide_overlapping=True,

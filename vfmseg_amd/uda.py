@@ -44,6 +44,8 @@ def choose_classes(class_lists):
 
 @MODELS.register_module()
 class DACS(EncoderDecoder):
+    _full_finetune_ok = False   # a bare DinoVisionTransformer in train() mode is refused by name (EncoderDecoder._tokens)
+
     def __init__(self, **cfg):
         missing = [k for k in _KEYS if k not in cfg]
         if missing:
