@@ -295,6 +295,16 @@ int vfm_rein_mix_fwd(const float* x, long ld_x, const void* t, const void* vt, v
 int vfm_rein_mix_bwd(const void* du, long ld_du, const void* p, long ld_p, const void* v, const void* tt, void* ds, long ld_ds,
                      float* dx, long ld_dx, long rows, int D, int m, float c, void* stream);
 
+/* LoRA down-projection of an adapter site whose input no LayerNorm kernel produces (DINOv2 attn.proj: the attention output, fc2: the
+ * GELU output), ONE launch over x [rows, K] in the 16-bit type (K % 128 == 0, x and a 16-byte aligned, leading dimensions % 8 == 0):
+ *   mask [rows, K] = the dropout multiplier, bit-identical to vfm_dropout_mask(contiguous [rows, K], p, seed, offset),
+ *   xd   [rows, K] = x * mask, bit-identical to vfm_mul_mask,
+ *   t    [rows, 64] = s * xd @ a^T (fp32 accumulation of the 16-bit MFMA) - usually the K tail of x's own buffer.
+ * a: [64, K], rows past the rank zero (all 64 columns of t are written for every row).  p == 0: mask and xd are not written (may be
+ * NULL) and t = s * x @ a^T. */
+int vfm_lora_down(const void* x, long ld_x, const void* a, long ld_a, void* mask, long ld_mask, void* xd, long ld_xd, void* t, long ld_t,
+                  long rows, long K, float s, float p, uint64_t seed, uint64_t offset, void* stream);
+
 /* Flash-style forward of the same attention (inference; head dim 80 = SAM ViT-H): token-major qkv [nimg*G*G, 3*H*d] -> token-major
  * out [nimg*G*G, H*d] in ONE launch - windows of S = 14 on the zero-padded grid (padded tokens: k / v = projection bias) or global
  * attention (S = G = 32).  tbl_h / tbl_w: bf16 [2*SP, d] (SP = 16 for S = 14, 32 for S = 32) relative-index tables,

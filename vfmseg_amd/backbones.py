@@ -8,7 +8,8 @@ The nn.Modules below are *parameter containers* that reproduce the reference's s
   residual      : fp32 [M, D]; GEMM operands in the compute dtype (bf16 | f32), fp32 accumulation.
   LoRA          : fused into the QKV projection by K-concatenation: [LN(x) | s*drop(LN(x)) A^T] @ [W | B]^T, so
                   the rank-32 path costs no extra pass over the activations (peft lora.Linear semantics,
-                  lora_backbone.py:16-23; scaling alpha/r).
+                  lora_backbone.py:16-23; scaling alpha/r).  attn.proj, fc1 and fc2 take the same form when
+                  Lora_config.target_modules names them (DinoEngine.sites()).
   backward      : hand-written (frozen base => only activation gradients + LoRA A/B weight gradients).
   full training : a bare DinoVisionTransformer in train() mode trains every base weight that enters the graph
                   (DinoEngine._backward_full: the weight / bias / LayerNorm / LayerScale / embedding gradients on top of the
@@ -315,6 +316,24 @@ class _PeftModel(nn.Module):
         self.base_model = _Holder(m)
 
 
+DINO_LORA_TARGETS = ("qkv", "attn.proj", "fc1", "fc2")   # Lora_config.target_modules the DinoEngine fuses (any non-empty subset)
+
+
+def check_dino_lora_config(targets, r):
+    """What LoRABackbone over a DinoVisionTransformer refuses, by the option's name (no GPU needed to ask)."""
+    if not targets:
+        raise ValueError(f"Lora_config.target_modules is empty: name at least one of {list(DINO_LORA_TARGETS)}")
+    for t in targets:
+        if t == "proj":
+            raise NotImplementedError("Lora_config.target_modules=['proj'] would also wrap the patch embedding's Conv2d (patch_embed.proj), "
+                                      "which is not on the HIP path: write 'attn.proj'")
+        if t not in DINO_LORA_TARGETS:
+            raise NotImplementedError(f"Lora_config.target_modules: {t!r} is no adapter site of the DinoVisionTransformer HIP engine; "
+                                      f"the sites are {list(DINO_LORA_TARGETS)}")
+    if not 1 <= int(r) <= R_PAD:
+        raise NotImplementedError(f"Lora_config.r={r}: the HIP engine pads the rank to one MFMA K-block, 1 <= r <= {R_PAD}")
+
+
 @MODELS.register_module()
 class LoRABackbone(nn.Module):
     """rein/models/backbones/lora_backbone.py:10-44.  `checkpoint=None` (random init) is accepted - a documented
@@ -325,9 +344,13 @@ class LoRABackbone(nn.Module):
         vit = MODELS.build(backbone)
         cfg = Lora_config or {}
         self.lora_targets = list(cfg.get("target_modules", ["qkv"]))
+        if isinstance(vit, DinoVisionTransformer):
+            check_dino_lora_config(self.lora_targets, cfg.get("r", 32))
+        self.lora_wrapped = []    # dotted names (inside the ViT) of the linear layers that carry an adapter
         # peft: a module is wrapped when its dotted name equals a target or ends with '.' + target
         for name, mod in list(vit.named_modules()):
             if isinstance(mod, _Lin) and any(name == t or name.endswith("." + t) for t in self.lora_targets):
+                self.lora_wrapped.append(name)
                 parent = vit
                 parts = name.split(".")
                 for p_ in parts[:-1]:
@@ -348,10 +371,19 @@ class LoRABackbone(nn.Module):
     def load_pretrained_backbone(self, checkpoint, target_modules):
         sd = torch.load(checkpoint, map_location="cpu") if isinstance(checkpoint, str) else checkpoint
         new = {}
+        dino = isinstance(self.vit, DinoVisionTransformer)
+        wrapped = set(self.lora_wrapped)
         for name, w in sd.items():
-            for t in target_modules:  # lora_backbone.py:30-34 rename
-                if t in name:
-                    name = name.replace(t, t + ".base_layer")
+            if dino:
+                # only the keys of modules that carry an adapter move under `.base_layer` (what lora_backbone.py:30-34 does for these
+                # targets by substring): keyed on the wrapped module, no other key - `patch_embed.proj.*` - can ever be renamed with them
+                mod, _, leaf = name.rpartition(".")
+                if mod in wrapped:
+                    name = mod + ".base_layer." + leaf
+            else:
+                for t in target_modules:  # lora_backbone.py:30-34 rename
+                    if t in name:
+                        name = name.replace(t, t + ".base_layer")
             new[name] = w
         self.vit.load_state_dict(new, strict=False)
         self.vit.engine().invalidate()
@@ -411,6 +443,31 @@ class Packed:
         if self.wt is not None:
             return ops.gemm(dy, self.wt, out, **epi)
         return ops.gemm(dy, self.w, out, trans_b=True, **epi)
+
+    def dgrad_cols(self, dy, out, c0, c1, **epi):
+        """dgrad restricted to the input columns [c0, c1) (a K-extended weight [W | B]: the base part and the LoRA tail apart)."""
+        if self.wt is not None:
+            return ops.gemm(dy, self.wt[c0:c1], out, **epi)
+        return ops.gemm(dy, self.w[:, c0:c1], out, trans_b=True, **epi)
+
+
+SITE_KEYS = ("qkv", "proj", "fc1", "fc2")   # DinoEngine's adapter sites, in the order of their factors within a block
+
+
+def _site_mod(blk, key):
+    return getattr(blk.attn if key in ("qkv", "proj") else blk.mlp, key)
+
+
+def _site_ops(key):
+    """names of a site's padded A [R_PAD, in] and A^T [in, R_PAD] operands in the packed layer dict"""
+    return ("a", "at") if key == "qkv" else ("a_" + key, "at_" + key)
+
+
+def lora_fused():
+    """VFMSEG_LORA_FUSED=1: the sites whose input no LayerNorm kernel produces (attn.proj, fc2) take vfm_lora_down in the 16-bit modes;
+    0 (default): the composed dropout_mask + mul_mask + gemm form (always in f32 / bf16x3 storage), which measures faster - 41 against
+    82 us at K = 4096, 16.6 against 17.7 ms per all-sites train step - as with VFMSEG_REIN_FUSED."""
+    return os.environ.get("VFMSEG_LORA_FUSED", "0") == "1"
 
 
 def wgrad(dy, x, grad_out, alpha=1.0, n_rows=None, accumulate=True):
@@ -584,8 +641,13 @@ class DinoEngine:
         self._packed = None
         self._pos_cache = {}
 
+    def sites(self):
+        """The adapted linear layers of a block (LoRABackbone wraps the same ones in every block), in SITE_KEYS order."""
+        b0 = self.vit.blocks[0]
+        return tuple(k for k in SITE_KEYS if isinstance(_site_mod(b0, k), LoraLinear))
+
     def lora_on(self):
-        return isinstance(self.vit.blocks[0].attn.qkv, LoraLinear)
+        return bool(self.sites())
 
     def rein_on(self):
         return getattr(self.vit, "reins", None) is not None
@@ -627,9 +689,11 @@ class DinoEngine:
         out = []
         if self.full_on():
             return self.full_params()
-        if self.lora_on():
-            for blk in self.vit.blocks:
-                out += [blk.attn.qkv.lora_A["default"].weight, blk.attn.qkv.lora_B["default"].weight]
+        sites = self.sites()
+        for blk in (self.vit.blocks if sites else ()):   # block order; within a block qkv, proj, fc1, fc2 (backward() hands back this order)
+            for k in sites:
+                m = _site_mod(blk, k)
+                out += [m.lora_A["default"].weight, m.lora_B["default"].weight]
         if self.rein_on():   # (after the per-block LoRA factors: backward() returns its gradients in this order)
             out += self.vit.reins.live_params()
         return out
@@ -665,25 +729,22 @@ class DinoEngine:
             P["pe_b"] = v.patch_embed.proj.bias.detach().float().contiguous()
             P["cls"] = v.cls_token.detach().reshape(D).float().contiguous()
             for blk in v.blocks:
-                qkv = blk.attn.qkv
-                base = qkv.base_layer if isinstance(qkv, LoraLinear) else qkv
-                kq = D + (R_PAD if isinstance(qkv, LoraLinear) else 0)
-                Lp = dict(
-                    qkv=Packed(base.weight.detach(), cd, k_pad=kq),
-                    qkv_b=base.bias.detach().float().contiguous() if base.bias is not None else None,
-                    proj=Packed(blk.attn.proj.weight.detach(), cd),
-                    proj_b=blk.attn.proj.bias.detach().float().contiguous() if blk.attn.proj.bias is not None else None,
-                    fc1=Packed(blk.mlp.fc1.weight.detach(), cd),
-                    fc1_b=blk.mlp.fc1.bias.detach().float().contiguous() if blk.mlp.fc1.bias is not None else None,
-                    fc2=Packed(blk.mlp.fc2.weight.detach(), cd),
-                    fc2_b=blk.mlp.fc2.bias.detach().float().contiguous() if blk.mlp.fc2.bias is not None else None,
+                Lp = {}
+                for key in SITE_KEYS:   # an adapted site's weight is packed as [W | B]: K extended by the padded rank
+                    m = _site_mod(blk, key)
+                    base = m.base_layer if isinstance(m, LoraLinear) else m
+                    kin = base.in_features
+                    Lp[key] = Packed(base.weight.detach(), cd, k_pad=kin + (R_PAD if isinstance(m, LoraLinear) else 0))
+                    Lp[key + "_b"] = base.bias.detach().float().contiguous() if base.bias is not None else None
+                    if isinstance(m, LoraLinear):
+                        na, nat = _site_ops(key)
+                        Lp[na] = torch.zeros(R_PAD, kin, dtype=cd, device=dev)       # A padded to 64 rows   [r, in]
+                        Lp[nat] = torch.zeros(kin, R_PAD, dtype=cd, device=dev)      # A^T                   [in, r]
+                Lp.update(
                     g1=blk.ls1.gamma.detach().float().contiguous(), g2=blk.ls2.gamma.detach().float().contiguous(),
                     n1w=blk.norm1.weight.detach().float().contiguous(), n1b=blk.norm1.bias.detach().float().contiguous(),
                     n2w=blk.norm2.weight.detach().float().contiguous(), n2b=blk.norm2.bias.detach().float().contiguous(),
                 )
-                if isinstance(qkv, LoraLinear):
-                    Lp["a"] = torch.zeros(R_PAD, D, dtype=cd, device=dev)       # A padded to 64 rows   [r, in]
-                    Lp["at"] = torch.zeros(D, R_PAD, dtype=cd, device=dev)      # A^T                   [in, r]
                 P["layers"].append(Lp)
         self._packed = P
         return P
@@ -730,41 +791,46 @@ class DinoEngine:
         return P
 
     def refresh_lora(self, P):
-        """LoRA factors change every optimiser step: re-pack them into the concatenated QKV operand (one launch)."""
-        D = self.vit.embed_dim
+        """LoRA factors change every optimiser step: re-pack them into the concatenated operands of every adapted site (one launch)."""
         sites = []
+        keys = self.sites()
         for blk, Lp in zip(self.vit.blocks, P["layers"]):
-            q = blk.attn.qkv
-            if isinstance(q, LoraLinear):
+            for key in keys:
+                q = _site_mod(blk, key)
+                na, nat = _site_ops(key)
                 A, Bm = q.lora_A["default"].weight.detach(), q.lora_B["default"].weight.detach()
-                sites.append((A, Bm, Lp["a"], Lp["at"], Lp["qkv"].w, Lp["qkv"].wt, q.r, A.shape[1], Bm.shape[0], D))
+                sites.append((A, Bm, Lp[na], Lp[nat], Lp[key].w, Lp[key].wt, q.r, A.shape[1], Bm.shape[0], A.shape[1]))
         _refresh_sites(P, sites)
 
-    def merged_qkv(self, P):
-        """Inference only (no LoRA dropout): per layer the bf16 copy of W + s * B A, so that the QKV projection is ONE K = D GEMM
-        (no T = x A^T GEMM, no K extension).  Rebuilt when a LoRA factor changed (torch version counters, data pointers, and
-        the optimiser's epoch for the fused AdamW kernel that updates parameters behind torch's back)."""
+    def merged_weights(self, P):
+        """Inference only (no LoRA dropout): per adapted site and layer the compute-dtype copy of W + s * B A, so that the projection is
+        ONE GEMM of the base shape (no T = x A^T product, no K extension).  Rebuilt when a LoRA factor changed (torch version counters,
+        data pointers, and the optimiser's epoch for the fused AdamW kernel that updates parameters behind torch's back).
+        Returns {site: [per-layer weight]}."""
         from .optim import PARAM_EPOCH
-        key = [PARAM_EPOCH[0]]
+        keys = self.sites()
+        key = [PARAM_EPOCH[0], keys]
         for blk in self.vit.blocks:
-            q = blk.attn.qkv
-            A, Bm = q.lora_A["default"].weight, q.lora_B["default"].weight
-            key += [A._version, Bm._version, A.data_ptr(), Bm.data_ptr()]
+            for k in keys:
+                q = _site_mod(blk, k)
+                A, Bm = q.lora_A["default"].weight, q.lora_B["default"].weight
+                key += [A._version, Bm._version, A.data_ptr(), Bm.data_ptr()]
         key = tuple(key)
         if P.get("merged_key") == key:
             return P["merged"]
-        D, cd, dev = self.vit.embed_dim, P["cd"], P["dev"]
-        merged = []
+        cd, dev = P["cd"], P["dev"]
+        merged = {k: [] for k in keys}
         with torch.no_grad():
             for blk in self.vit.blocks:
-                q = blk.attn.qkv
-                A, Bm = q.lora_A["default"].weight.detach().float(), q.lora_B["default"].weight.detach().float()
-                w = q.base_layer.weight.detach().float()
-                weff = torch.empty_like(w)
-                ops.gemm(Bm.contiguous(), A.contiguous(), weff, alpha=q.scaling, residual=w, trans_b=True)   # W + s * B A   (fp32 MFMA)
-                wp = ops.empty_ld(w.shape[0], D, cd, dev)
-                ops.cast(weff, wp)
-                merged.append(wp)
+                for k in keys:
+                    q = _site_mod(blk, k)
+                    A, Bm = q.lora_A["default"].weight.detach().float(), q.lora_B["default"].weight.detach().float()
+                    w = q.base_layer.weight.detach().float()
+                    weff = torch.empty_like(w)
+                    ops.gemm(Bm.contiguous(), A.contiguous(), weff, alpha=q.scaling, residual=w, trans_b=True)   # W + s * B A   (fp32 MFMA)
+                    wp = ops.empty_ld(w.shape[0], w.shape[1], cd, dev)
+                    ops.cast(weff, wp)
+                    merged[k].append(wp)
         P["merged"], P["merged_key"] = merged, key
         return merged
 
@@ -794,15 +860,16 @@ class DinoEngine:
         cd = P["cd"]
         dev = P["dev"]
         D, H, ps = v.embed_dim, v.num_heads, v.patch_size
-        lora = self.lora_on()
+        sites = self.sites()
+        lora = "qkv" in sites      # (the QKV site: the LN1-fed branch below; the other sites are `ext`)
         rein = self._rein_pack(P) if self.rein_on() else None
         merged = None
         from .precision import split3 as _x3_mode
         x3 = _x3_mode() and not is_half(cd)
-        if (lora and not training and not torch.is_grad_enabled() and (is_half(cd) or x3)
+        if (sites and not training and not torch.is_grad_enabled() and (is_half(cd) or x3)
                 and os.environ.get("VFMSEG_MERGE_LORA_EVAL", "1") != "0"):
-            merged = self.merged_qkv(P)
-        elif lora:
+            merged = self.merged_weights(P)
+        elif sites:
             self.refresh_lora(P)
         sizes = []
         for img, box in jobs:
@@ -836,9 +903,18 @@ class DinoEngine:
         tap_dt = torch.float32 if (not training and not need_grad and eval_heads_fp32()) else cd
         xcat = torch.empty(Mp, nt * D, dtype=tap_dt, device=dev)
         saved = []
-        if lora and training:
+        hid = P["layers"][0]["fc1"].n
+        # dropout counters: one region of nL * M * width per site, laid end to end in SITE_KEYS order (disjoint streams); a call reserves up
+        # to the end of its last adapted site - a qkv-only model nL * M * D, its seeds, offsets and masks are what they always were
+        rng_site, end, rng_n = {}, 0, 0
+        for k in SITE_KEYS:
+            rng_site[k] = end
+            end += len(v.blocks) * M * (hid if k == "fc2" else D)
+            if k in sites:
+                rng_n = end
+        if sites and training:
             from .functional import draw_seed
-            seed, rng0 = draw_seed(seed, len(v.blocks) * M * D)
+            seed, rng0 = draw_seed(seed, rng_n)
         else:
             seed, rng0 = 0, 0
         if plan is not None:
@@ -883,33 +959,69 @@ class DinoEngine:
                 ops.gemm(xd, Lp["a"], a1[:, D:D + R_PAD], alpha=q.scaling)  # T = s * drop(xn) A^T
                 S.update(xd=xd if mask is not None else None, mask=mask)
             qkv = torch.empty(M, 3 * D, dtype=cd, device=dev)
-            if merged is not None:
-                ops.gemm(a1, merged[li], qkv, bias=Lp["qkv_b"])
+            if merged is not None and lora:
+                ops.gemm(a1, merged["qkv"][li], qkv, bias=Lp["qkv_b"])
             else:
                 Lp["qkv"].fwd(a1, qkv, bias=Lp["qkv_b"])
-            ao = torch.empty(M, D, dtype=cd, device=dev)
+            # the other adapter sites, unmerged: the operand is [x | T] with x the site's input in the first K columns of a buffer whose
+            # leading dimension is K + R_PAD (the producers below write strided views) and the weight is packed as [W | B]
+            ext = {k: (k in sites and merged is None) for k in ("proj", "fc1", "fc2")}
+            S["lora"] = {}
+            ao_op = torch.empty(M, D + (R_PAD if ext["proj"] else 0), dtype=cd, device=dev)
+            ao = ao_op[:, :D] if ext["proj"] else ao_op
             lse = torch.empty(nimg, H, Np + 1, dtype=torch.float32, device=dev)
             so = "only" if (x3 and not training and not need_grad) else None
-            ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, lse, nimg, H, hd, Np, 1, Np, 1, scale, keep_split=training, o_split=so)
+            ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, lse, nimg, H, hd, Np, 1, Np, 1, scale, keep_split=training,
+                         o_split=None if ext["proj"] else so)
+            if ext["proj"]:
+                S["lora"]["proj"] = self._lora_down(blk.attn.proj, Lp["a_proj"], ao_op, D, training, seed, rng0 + rng_site["proj"] + li * M * D)
             xm = torch.empty(M, D, dtype=torch.float32, device=dev)
             # full fine-tuning: the epilogue's second output is the branch output BEFORE the LayerScale column scale (bias included) -
             # what d gamma reads; x_mid / x_out themselves are what every other caller gets
             u1 = torch.empty(M, D, dtype=cd, device=dev) if full else None
             u2 = torch.empty(M, D, dtype=cd, device=dev) if full else None
-            Lp["proj"].fwd(ao, xm, bias=Lp["proj_b"], colscale=Lp["g1"], residual=x, **({"c2": u1} if full else {}))
-            a2 = torch.empty(M, D, dtype=cd, device=dev)
+            if merged is not None and "proj" in sites:
+                ops.gemm(ao, merged["proj"][li], xm, bias=Lp["proj_b"], colscale=Lp["g1"], residual=x)
+            else:
+                Lp["proj"].fwd(ao_op, xm, bias=Lp["proj_b"], colscale=Lp["g1"], residual=x, **({"c2": u1} if full else {}))
+            a2_op = torch.empty(M, D + (R_PAD if ext["fc1"] else 0), dtype=cd, device=dev)
+            a2 = a2_op[:, :D] if ext["fc1"] else a2_op
             st2 = torch.empty(M, 2, dtype=torch.float32, device=dev)
-            ops.layernorm_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2, split_out=so)
-            hid = Lp["fc1"].n
-            g = ops.empty_ld(M, hid, cd, dev)
-            if training and (lora or (rein is not None and need_grad) or full):   # the forward also saves gelu'(pre-activation): what fc2's dgrad multiplies by (mlp.py:34-40)
+            if ext["fc1"]:    # fed by LayerNorm 2 as the QKV site is by LayerNorm 1: LN + dropout multiplier + dropped copy in one pass
+                q1 = blk.mlp.fc1
+                off1 = rng0 + rng_site["fc1"] + li * M * D
+                xd1 = mask1 = None
+                if training and q1.p > 0:
+                    mask1, xd1 = torch.empty(M, D, dtype=cd, device=dev), torch.empty(M, D, dtype=cd, device=dev)
+                    if is_half(cd) and D % 256 == 0:
+                        ops.layernorm_dropout_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2, xd1, mask1, q1.p, seed, offset=off1)
+                    else:
+                        ops.layernorm_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2)
+                        ops.dropout_mask(mask1, q1.p, seed, offset=off1)
+                        ops.mul_mask(a2, mask1, xd1)
+                else:
+                    ops.layernorm_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2)
+                ops.gemm(xd1 if xd1 is not None else a2, Lp["a_fc1"], a2_op[:, D:D + R_PAD], alpha=q1.scaling)
+                S["lora"]["fc1"] = (xd1, mask1)
+            else:
+                ops.layernorm_fwd(xm, Lp["n2w"], Lp["n2b"], 1e-6, a2, st2, split_out=so)
+            g_op =torch.empty(M, hid + R_PAD, dtype=cd, device=dev) if ext["fc2"] else None
+            g = g_op[:, :hid] if ext["fc2"] else ops.empty_ld(M, hid, cd, dev)
+            w1 = merged["fc1"][li] if (merged is not None and "fc1" in sites) else Lp["fc1"].w
+            if training and (sites or (rein is not None and need_grad) or full):   # the forward also saves gelu'(pre-activation): what fc2's dgrad multiplies by (mlp.py:34-40)
                 hpre = torch.empty(M, hid, dtype=cd, device=dev)
-                Lp["fc1"].fwd(a2, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU_DGELU, c2=hpre)
+                ops.gemm(a2_op, w1, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU_DGELU, c2=hpre)
             else:
                 hpre = None
-                Lp["fc1"].fwd(a2, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU, **({"c_split": so} if so else {}))
+                ops.gemm(a2_op, w1, g, bias=Lp["fc1_b"], ep_mode=ops.EP_GELU, **({"c_split": so} if (so and not ext["fc2"]) else {}))
+            if ext["fc2"]:
+                S["lora"]["fc2"] = self._lora_down(blk.mlp.fc2, Lp["a_fc2"], g_op, hid, training, seed, rng0 + rng_site["fc2"] + li * M * hid)
             xo = torch.empty(M, D, dtype=torch.float32, device=dev)
-            Lp["fc2"].fwd(g, xo, bias=Lp["fc2_b"], colscale=Lp["g2"], residual=xm, **({"c2": u2} if full else {}))
+            if merged is not None and "fc2" in sites:
+                ops.gemm(g, merged["fc2"][li], xo, bias=Lp["fc2_b"], colscale=Lp["g2"], residual=xm)
+            else:
+                Lp["fc2"].fwd(g_op if ext["fc2"] else g, xo, bias=Lp["fc2_b"], colscale=Lp["g2"], residual=xm, **({"c2": u2} if full else {}))
+            S.update(ao_op=ao_op, a2_op=a2_op, g_op=g_op)
             S.update(a1=a1, st1=st1, qkv=qkv, ao=ao, lse=lse, x_mid=xm, a2=a2, st2=st2, hpre=hpre, g=g, u1=u1, u2=u2)
             saved.append(S)
             x = xo
@@ -922,11 +1034,33 @@ class DinoEngine:
                    full=full, A0=A0 if full else None)
         return xcat, (hp, wp), ctx
 
+    @staticmethod
+    def _lora_down(q, a_op, buf, K, training, seed, offset):
+        """buf [M, K + R_PAD] holds the adapter input x of site q in its first K columns; writes T = s * drop(x) A^T into the K tail (all
+        R_PAD columns: A is zero-padded).  Returns (xd, mask) - the dropped copy and the multiplier backward reads - or (None, None)
+        without dropout.  dropout_mask + mul_mask + gemm, or with VFMSEG_LORA_FUSED=1 in the 16-bit modes ONE launch (vfm_lora_down),
+        which writes the same mask and xd bits."""
+        x, T = buf[:, :K], buf[:, K:K + R_PAD]
+        drop = bool(training and q.p > 0)
+        xd = mask = None
+        if drop:
+            mask = torch.empty(x.shape[0], K, dtype=x.dtype, device=x.device)
+            xd = torch.empty(x.shape[0], K, dtype=x.dtype, device=x.device)
+        if lora_fused() and ops.lora_down_ok(x, a_op):
+            ops.lora_down(x, a_op, T, q.scaling, q.p if drop else 0.0, seed, offset, mask, xd)
+        else:
+            if drop:
+                ops.dropout_mask(mask, q.p, seed, offset=offset)
+                ops.mul_mask(x, mask, xd)
+            ops.gemm(xd if drop else x, a_op, T, alpha=q.scaling)
+        return xd, mask
+
     def _train_plan(self, P, nimg, Np, training, merged):
-        """The launch plan of this call's shape when the call is the hot one (training with gradients, LoRA with dropout on every
-        block, 16-bit mode, weight gradients into the optimiser's flat buffer) and no earlier forward still owns the plan's buffers."""
+        """The launch plan of this call's shape when the call is the hot one (training with gradients, LoRA on the QKV site alone with
+        dropout on every block, 16-bit mode, weight gradients into the optimiser's flat buffer) and no earlier forward still owns the
+        plan's buffers.  Other adapter sites run on the one-by-one path."""
         v = self.vit
-        if (not training or merged is not None or not self.lora_on() or self.rein_on() or not is_half(P["cd"])
+        if (not training or merged is not None or self.sites() != ("qkv",) or self.rein_on() or not is_half(P["cd"])
                 or os.environ.get("VFMSEG_PLAN", "1") == "0" or v.embed_dim % 256 != 0):
             return None
         q0 = v.blocks[0].attn.qkv
@@ -949,7 +1083,7 @@ class DinoEngine:
                 plan.run_backward(ctx, dxcat)
             finally:
                 plan.busy = False
-            return [None] * (2 * len(self.vit.blocks))
+            return [None] * (2 * len(self.vit.blocks))      # (the plan runs qkv-only models)
         if ctx.get("full"):
             return self._backward_full(ctx, dxcat)
         v, P = self.vit, ctx["P"]
@@ -959,7 +1093,10 @@ class DinoEngine:
         scale = hd ** -0.5
         M, Mp, nimg, Np = ctx["M"], ctx["Mp"], ctx["nimg"], ctx["Np"]
         dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
-        grads = [None] * (2 * len(v.blocks) if self.lora_on() else 0)
+        sites = self.sites()
+        ns = len(sites)
+        grads = [None] * (2 * ns * len(v.blocks))    # trainable() order: per block, per adapted site, (A, B)
+        gidx = {k: 2 * i for i, k in enumerate(sites)}
         nL = len(v.blocks)
         rein = ctx.get("rein")
         rein_acc = self._rein_backward_begin(rein) if rein is not None else None
@@ -969,7 +1106,7 @@ class DinoEngine:
         # per half of the backbone - no split-K, no slabs - plus one batched scatter into the flat gradient buffer.  Two halves so
         # that the first LoRA gradient bucket can still leave (DP) while the second half of the backward runs.
         from .functional import direct_grad_target
-        wg_batched = (ctx.get("A1all") is not None and self.lora_on() and os.environ.get("VFMSEG_LORA_WGRAD_BATCHED", "1") != "0" and
+        wg_batched = (ctx.get("A1all") is not None and "qkv" in sites and os.environ.get("VFMSEG_LORA_WGRAD_BATCHED", "1") != "0" and
                       all(direct_grad_target(b.attn.qkv.lora_A["default"].weight) is not None and
                           direct_grad_target(b.attn.qkv.lora_B["default"].weight) is not None for b in v.blocks) and
                       (ctx.get("XDall") is not None or all(S_["mask"] is None for S_ in ctx["saved"])))
@@ -1000,9 +1137,30 @@ class DinoEngine:
                 ops.cast(dx, t, Lp["g2"])
             hid = Lp["fc1"].n
             dh = ops.empty_ld(M, hid, cd, dev)
-            Lp["fc2"].dgrad(t, dh, ep_mode=ops.EP_MUL, aux=S["hpre"])
-            dn = torch.empty(M, D, dtype=cd, device=dev)
-            Lp["fc1"].dgrad(dh, dn)
+            SL = S.get("lora") or {}
+            g0 = 2 * ns * li
+            if "fc2" in SL:
+                # d g = t [W | B] has the base part dg0 = t W and the tail dT = t B; d h = gelu'(pre) * (dg0 + mask * (s dT A)): the first
+                # term is the dgrad epilogue as ever, the second the site's EP_MUL GEMM with gelu'(pre) * mask as its multiplier
+                xd2, mask2 = SL["fc2"]
+                Lp["fc2"].dgrad_cols(t, dh, 0, hid, ep_mode=ops.EP_MUL, aux=S["hpre"])
+                dT2 = torch.empty(M, R_PAD, dtype=cd, device=dev)
+                Lp["fc2"].dgrad_cols(t, dT2, hid, hid + R_PAD)
+                mul2 = S["hpre"]
+                if mask2 is not None:
+                    mul2 = torch.empty_like(S["hpre"])
+                    ops.mul_mask(S["hpre"], mask2, mul2)
+                self._site_backward(blk.mlp.fc2, Lp["at_fc2"], S["g_op"][:, hid:hid + R_PAD], t, dT2, dh,
+                                    xd2 if xd2 is not None else S["g"], mul2, grads, g0 + gidx["fc2"])
+            else:
+                Lp["fc2"].dgrad(t, dh, ep_mode=ops.EP_MUL, aux=S["hpre"])
+            dn_op = torch.empty(M, Lp["fc1"].k, dtype=cd, device=dev)
+            Lp["fc1"].dgrad(dh, dn_op)
+            dn = dn_op[:, :D] if "fc1" in SL else dn_op
+            if "fc1" in SL:
+                xd1, mask1 = SL["fc1"]
+                self._site_backward(blk.mlp.fc1, Lp["at_fc1"], S["a2_op"][:, D:D + R_PAD], dh, dn_op[:, D:D + R_PAD], dn,
+                                    xd1 if xd1 is not None else S["a2"], mask1, grads, g0 + gidx["fc1"])
             if fuse_t:
                 ops.layernorm_bwd_scaled(dn, S["x_mid"], Lp["n2w"], S["st2"], dx, t, Lp["g1"], accumulate_dx=True)
             else:
@@ -1010,8 +1168,13 @@ class DinoEngine:
                 ops.cast(dx, t, Lp["g1"])
             del dh
             # ---- attention branch: x_mid = x_in + g1 * proj(attn(qkv(LN1(x_in))))
-            dao = torch.empty(M, D, dtype=cd, device=dev)
-            Lp["proj"].dgrad(t, dao)
+            dao_op = torch.empty(M, Lp["proj"].k, dtype=cd, device=dev)
+            Lp["proj"].dgrad(t, dao_op)
+            dao = dao_op[:, :D] if "proj" in SL else dao_op
+            if "proj" in SL:
+                xdp, maskp = SL["proj"]
+                self._site_backward(blk.attn.proj, Lp["at_proj"], S["ao_op"][:, D:D + R_PAD], t, dao_op[:, D:D + R_PAD], dao,
+                                    xdp if xdp is not None else S["ao"], maskp, grads, g0 + gidx["proj"])
             dqkv = DQKVall[li] if wg_batched else torch.empty(M, 3 * D, dtype=cd, device=dev)
             qkv = S["qkv"]
             ops.attn_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], S["ao"], S["lse"], dao, dqkv[:, :D], dqkv[:, D:2 * D],
@@ -1024,36 +1187,9 @@ class DinoEngine:
                 ep = dict(ep_mode=ops.EP_MUL, aux=S["mask"]) if S["mask"] is not None else {}
                 ops.gemm(da1[:, D:D + R_PAD], Lp["at"], da1[:, :D], alpha=q.scaling, residual=da1[:, :D], **ep)
             elif isinstance(q, LoraLinear):
-                r = q.r
-                A, Bm = q.lora_A["default"].weight, q.lora_B["default"].weight
                 a1 = S["a1"]
-                xd = S["xd"] if S["xd"] is not None else a1[:, :D]
-                # dB^T[r, out] = T^T @ dqkv ;  dA[r, in] = s * dT^T @ drop(xn)   (reductions over the M tokens)
-                from .functional import direct_grad_target
-                tB, tA = direct_grad_target(Bm), direct_grad_target(A)
-                gBt = torch.empty(R_PAD, Bm.shape[0], dtype=torch.float32, device=dev)
-                gAp = torch.empty(R_PAD, A.shape[1], dtype=torch.float32, device=dev)
-                # with a flat gradient buffer the split-K combine scatters straight into B.grad [out, r] / A.grad [r, in]
-                doneB = _wgrad_small_t(a1[:, D:D + R_PAD], dqkv, gBt, scatter=None if tB is None else (tB, r, 1, r))
-                doneA = _wgrad_small_t(da1[:, D:D + R_PAD], xd, gAp, alpha=q.scaling,
-                                       scatter=None if tA is None else (tA, r, A.shape[1], 1))
-                if doneB is True:
-                    pass
-                elif tB is not None:
-                    ops.strided_copy(gBt, tB, (Bm.shape[0], r), (1, gBt.stride(0)), (r, 1), accumulate=True)
-                else:
-                    gB = torch.empty_like(Bm, dtype=torch.float32)
-                    ops.strided_copy(gBt, gB, (Bm.shape[0], r), (1, gBt.stride(0)), (r, 1))
-                    grads[2 * li + 1] = gB
-                if doneA is True:
-                    pass
-                elif tA is not None:
-                    ops.axpby(gAp[:r].reshape(-1), 1.0, tA.view(-1), 1.0)
-                else:
-                    grads[2 * li] = gAp[:r]
-                # d LN1(x) = da1[:, :D] + mask * (s * dT @ A)
-                ep = dict(ep_mode=ops.EP_MUL, aux=S["mask"]) if S["mask"] is not None else {}
-                ops.gemm(da1[:, D:D + R_PAD], Lp["at"], da1[:, :D], alpha=q.scaling, residual=da1[:, :D], **ep)
+                self._site_backward(q, Lp["at"], a1[:, D:D + R_PAD], dqkv, da1[:, D:D + R_PAD], da1[:, :D],
+                                    S["xd"] if S["xd"] is not None else a1[:, :D], S["mask"], grads, g0 + gidx["qkv"])
             if fuse_t1 and li > 0:  # dx becomes d(x_out) of block li-1: its tap gradient goes in first, then LN1 backward
                 add_tap(li - 1)     # accumulates and emits t = bf16(dx * g2[li-1]) for that block's fc2 dgrad
                 ops.layernorm_bwd_scaled(da1[:, :D], S["x_in"], Lp["n1w"], S["st1"], dx, t, P["layers"][li - 1]["g2"],
@@ -1074,6 +1210,39 @@ class DinoEngine:
         if rein is not None:
             grads += self._rein_backward_end(rein, rein_acc)
         return grads
+
+    @staticmethod
+    def _site_backward(q, at_op, T, dy, dT, dxv, xd, mul, grads, gi):
+        """One adapted site of one layer, after the dgrad GEMM d[x | T] = dy [W | B] wrote dxv = d x (base part) and dT:
+        the factor gradients dB^T[r, out] = T^T dy and dA[r, in] = s dT^T drop(x) (reductions over the M tokens; `xd` = drop(x), or x itself
+        without dropout) - into the optimiser's flat buffer where there is one, else grads[gi] / grads[gi + 1] - and then
+        dxv += mul * (s dT A) in place (`mul`: the dropout multiplier, None without dropout; fc2 passes gelu'(pre) [* mask])."""
+        from .functional import direct_grad_target
+        r = q.r
+        A, Bm = q.lora_A["default"].weight, q.lora_B["default"].weight
+        dev = dy.device
+        tB, tA = direct_grad_target(Bm), direct_grad_target(A)
+        gBt = torch.empty(R_PAD, Bm.shape[0], dtype=torch.float32, device=dev)
+        gAp = torch.empty(R_PAD, A.shape[1], dtype=torch.float32, device=dev)
+        # with a flat gradient buffer the split-K combine scatters straight into B.grad [out, r] / A.grad [r, in]
+        doneB = _wgrad_small_t(T, dy, gBt, scatter=None if tB is None else (tB, r, 1, r))
+        doneA = _wgrad_small_t(dT, xd, gAp, alpha=q.scaling, scatter=None if tA is None else (tA, r, A.shape[1], 1))
+        if doneB is True:
+            pass
+        elif tB is not None:
+            ops.strided_copy(gBt, tB, (Bm.shape[0], r), (1, gBt.stride(0)), (r, 1), accumulate=True)
+        else:
+            gB = torch.empty_like(Bm, dtype=torch.float32)
+            ops.strided_copy(gBt, gB, (Bm.shape[0], r), (1, gBt.stride(0)), (r, 1))
+            grads[gi + 1] = gB
+        if doneA is True:
+            pass
+        elif tA is not None:
+            ops.axpby(gAp[:r].reshape(-1), 1.0, tA.view(-1), 1.0)
+        else:
+            grads[gi] = gAp[:r]
+        ep = dict(ep_mode=ops.EP_MUL, aux=mul) if mul is not None else {}
+        ops.gemm(dT, at_op, dxv, alpha=q.scaling, residual=dxv, **ep)
 
     # ---- full fine-tuning: d(xcat) -> gradients of full_params(), in that order (None where they went into the flat buffer)
     @staticmethod

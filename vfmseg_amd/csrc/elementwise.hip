@@ -4,7 +4,7 @@
 thread_local char g_vfm_err[512] = {0};
 
 extern "C" const char* vfm_last_error(void) { return g_vfm_err; }
-extern "C" int vfm_abi_version(void) { return 12; }   // 2: launch plans (vfm_run_plan, vfm_prof_*); 3: vfm_gemm_desc.c_plane (c_dt VFM_SPLIT3); 4: vfm_resize_bilinear source scales; 5: vfm_resize_bicubic double scales; 6: the DACS entry points (vfm_upsample_ce_w, vfm_pseudo_label, vfm_class_presence, vfm_class_mix); 7: vfm_postprocess_argmax; 8: vfm_augment_u8; 9: the loss options (vfm_ohem_prob, vfm_ohem_threshold, vfm_label_weight); 10: gradient clipping (vfm_grad_norm, vfm_adamw_clip); 11: the Dice loss (vfm_upsample_dice_sums, vfm_dice_finish, vfm_upsample_dice_bwd); 12: full fine-tuning (vfm_branch_param_grads, vfm_pack_weights)
+extern "C" int vfm_abi_version(void) { return 13; }   // 2: launch plans (vfm_run_plan, vfm_prof_*); 3: vfm_gemm_desc.c_plane (c_dt VFM_SPLIT3); 4: vfm_resize_bilinear source scales; 5: vfm_resize_bicubic double scales; 6: the DACS entry points (vfm_upsample_ce_w, vfm_pseudo_label, vfm_class_presence, vfm_class_mix); 7: vfm_postprocess_argmax; 8: vfm_augment_u8; 9: the loss options (vfm_ohem_prob, vfm_ohem_threshold, vfm_label_weight); 10: gradient clipping (vfm_grad_norm, vfm_adamw_clip); 11: the Dice loss (vfm_upsample_dice_sums, vfm_dice_finish, vfm_upsample_dice_bwd); 12: full fine-tuning (vfm_branch_param_grads, vfm_pack_weights); 13: vfm_lora_down
 extern "C" int vfm_half_kind(void) { return VFM_HALF_KIND; }
 
 // ------------------------------------------------------------------------------------------------ cast

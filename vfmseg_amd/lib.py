@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvfmseg_hip.so")
 LIB_PATH_F16 = os.path.join(_HERE, "csrc", "libvfmseg_hip_f16.so")
 
 F32, BF16, U8, I64, SPLIT3 = 0, 1, 2, 3, 4
-ABI_VERSION = 12   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax, 8 vfm_augment_u8, 9 the loss options (vfm_ohem_prob, vfm_ohem_threshold, vfm_label_weight), 10 gradient clipping (vfm_grad_norm, vfm_adamw_clip), 11 the Dice loss (vfm_upsample_dice_sums, vfm_dice_finish, vfm_upsample_dice_bwd), 12 full fine-tuning (vfm_branch_param_grads, vfm_pack_weights): an older one lacks the symbols
+ABI_VERSION = 13   # include/vfmseg_hip.h: 3 vfm_gemm_desc.c_plane, 4 vfm_resize_bilinear source scales, 5 vfm_resize_bicubic double scales: an older in-tree .so would misread the calls; 6 the DACS entry points, 7 vfm_postprocess_argmax, 8 vfm_augment_u8, 9 the loss options (vfm_ohem_prob, vfm_ohem_threshold, vfm_label_weight), 10 gradient clipping (vfm_grad_norm, vfm_adamw_clip), 11 the Dice loss (vfm_upsample_dice_sums, vfm_dice_finish, vfm_upsample_dice_bwd), 12 full fine-tuning (vfm_branch_param_grads, vfm_pack_weights), 13 vfm_lora_down: an older one lacks the symbols
 EP_NONE, EP_GELU, EP_RELU, EP_MUL_GELU_GRAD, EP_MUL, EP_QGELU, EP_MUL_QGELU_GRAD, EP_GELU_DGELU = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_QGELU = 0, 1, 2, 3
 
@@ -158,6 +158,7 @@ SIGNATURES = {
     "vfm_softmax_rows_bwd": [vp, vp, cl, vp, ci, cl, cl, ci, ci, ci, ci, vp],
     "vfm_rein_mix_fwd": [vp, cl, vp, vp, vp, cl, vp, cl, vp, cl, cl, ci, ci, cf, vp],
     "vfm_rein_mix_bwd": [vp, cl, vp, cl, vp, vp, vp, cl, vp, cl, cl, ci, ci, cf, vp],
+    "vfm_lora_down": [vp, cl, vp, cl, vp, cl, vp, cl, vp, cl, cl, cl, cf, cf, u64, u64, vp],
     "vfm_sam_attn_bwd_merge": [vp, vp, vp, ci, vp, vp, vp, cl, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp],
     "vfm_sam_attn_flash_fwd": [vp, cl, vp, vp, vp, vp, cl, ci, ci, ci, ci, ci, cf, vp],
     "vfm_sam_attn_flash_fwd_train": [vp, cl, vp, vp, vp, vp, cl, ci, ci, ci, ci, ci, cf, vp, vp, vp],

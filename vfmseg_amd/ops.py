@@ -174,6 +174,32 @@ def mul_mask(src, mask, dst, rows_per_group=1):
     return dst
 
 
+LORA_DOWN_KC = 128   # vfm_lora_down stages K in chunks of 128
+
+
+def lora_down_ok(x, a):
+    """Does the fused LoRA down-projection kernel cover this operand?  (16-bit, K % 128 == 0, A padded to 64 rows, 16-byte alignment)"""
+    return (is_half(x.dtype) and a.dtype == x.dtype and x.shape[1] % LORA_DOWN_KC == 0 and a.shape == (64, x.shape[1]) and
+            x.stride(1) == 1 and a.stride(1) == 1 and x.stride(0) % 8 == 0 and a.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+            and a.data_ptr() % 16 == 0)
+
+
+def lora_down(x, a, t, s, p=0.0, seed=0, offset=0, mask=None, xd=None):
+    """One launch over x [M, K] (16 bit, may be a column slice): mask = dropout multiplier (the bits of dropout_mask on a contiguous
+    [M, K] map), xd = x * mask (the bits of mul_mask), t [M, 64] = s * xd @ a^T.  p == 0: no mask, no xd, t = s * x @ a^T."""
+    lib = L.load()
+    M, K = x.shape
+    assert lora_down_ok(x, a) and t.shape == (M, 64) and t.dtype == x.dtype and t.stride(1) == 1
+    if p > 0:
+        assert mask is not None and xd is not None and mask.shape == (M, K) and xd.shape == (M, K) and mask.dtype == x.dtype == xd.dtype
+    else:
+        mask = xd = None
+    L.check(lib.vfm_lora_down(L.ptr(x), _ld(x), L.ptr(a), _ld(a), L.ptr(mask), _ld(mask) if mask is not None else 0, L.ptr(xd),
+                              _ld(xd) if xd is not None else 0, L.ptr(t), _ld(t), M, K, float(s), float(p), int(seed), int(offset), L.stream()),
+            "vfm_lora_down")
+    return t
+
+
 def geglu_fwd(h, out):
     lib = L.load()
     rows, c2 = h.shape

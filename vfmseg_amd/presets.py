@@ -48,8 +48,12 @@ def dinov2_backbone(depth=24, embed_dim=1024, num_heads=16, img_size=512):
     )
 
 
-def lora_cfg(r=32, alpha=32, targets=("qkv",), dropout=0.1):
-    return dict(r=r, lora_alpha=alpha, target_modules=list(targets), lora_dropout=dropout)
+ALL_LINEAR = ("qkv", "attn.proj", "fc1", "fc2")   # every linear layer of a DINOv2 block (backbones.DINO_LORA_TARGETS)
+
+
+def lora_cfg(r=32, alpha=32, targets=("qkv",), dropout=0.1, target_modules=None):
+    """`target_modules` (peft's name for it) overrides `targets`."""
+    return dict(r=r, lora_alpha=alpha, target_modules=list(targets if target_modules is None else target_modules), lora_dropout=dropout)
 
 
 def linear_head(embed_dim=1024, channels=256, num_classes=19):
