@@ -55,7 +55,7 @@ def test_libraries_refuse_the_other_half_type(fp16_mode):
 def test_kernel_suites_against_the_fp16_twin():
     env = dict(os.environ, VFMSEG_TEST_HALF="fp16")
     # not re-run: the split-bf16 precision mode (bf16 by construction) and the off-by-default persistent-GEMM experiment
-    cmd = [sys.executable, "-m", "pytest", "tests/test_kernels_gpu.py", "tests/test_sam_flash_gpu.py", "tests/test_sam_window_gpu.py", "tests/test_elementwise_gpu.py", "tests/test_norm_gpu.py", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider",
+    cmd = [sys.executable, "-m", "pytest", "tests/test_kernels_gpu.py", "tests/test_sam_flash_gpu.py", "tests/test_sam_window_gpu.py", "tests/test_elementwise_gpu.py", "tests/test_norm_gpu.py", "tests/test_attention_gpu.py", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider",
            "-k", "not bf16x3 and not persistent and not experimental"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     tail = "\n".join(r.stdout.strip().splitlines()[-15:])
